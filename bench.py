@@ -11,9 +11,14 @@ N ranks itself through torch.distributed.run before this process touches the GPU
 (WORLD_SIZE set) each rank takes its own GPU (LOCAL_RANK) and the ranks check that their devices
 are distinct. The line reports the devices and the world size / backend torch.distributed saw.
 
-Also reported (side fields, rank 0): cfg 2 element-wise Fp127 add/mul at 2^24, full ct_mul WITH
-sigma (the reference's complete ct_mul) on a smaller batch, cfg 4 (GPU enc_value + depth-8
-chains over 2^16 inputs) and batched enc_value, each with its CPU baseline where one exists.
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and
+prints the line: value, ms_per_step and the HBM roofline of the dominant kernel from the HIP-event
+times of those same steps. `--dump-outputs DIR` also writes what the last timed step computed
+(dump_outputs below). Everything that takes runs of its own waits for `--full`: the self-checks
+(gsum invariant, shard digests), the PMC record and the measured VALU ceilings of the roofline, the
+same-host CPU baseline, and the side fields (rank 0): cfg 2 element-wise Fp127 add/mul at 2^24,
+full ct_mul WITH sigma (the reference's complete ct_mul) on a smaller batch, cfg 4 (GPU enc_value +
+depth-8 chains over 2^16 inputs) and batched enc_value, each with its CPU baseline where one exists.
 """
 import argparse
 import json
@@ -68,9 +73,19 @@ def parse():
                     help="pairs per rank whose digests rank 0 recomputes from global indices (shard check)")
     ap.add_argument("--topology-only", action="store_true",
                     help="launcher check: every rank reports its device and the process group, no GPU work")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the self-checks, the PMC / VALU-ceiling roofline fields, "
+                         "the CPU baseline and the side measurements (a plain run times the headline and stops)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; see dump_outputs)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no side measurements")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step is the mean over the timed steps)")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def _shared_ok():
@@ -336,39 +351,102 @@ def main():
             "step_GBs": step_bytes / (ms_per_step / 1000.0) / 1e9,
         },
         "cpu_baseline": None,
+        "full": bool(args.full),
     }
-    # HBM traffic and the VALU counters of the same kernel from the committed PMC record
-    # (tools/pmc_target.sh -> profiles/pmc/headline.json), quoted only when the record was taken on
-    # THIS library binary (sha256 of libpvac_hip.so) and this batch shape; null plus the reason else
-    pm, why = pmc_record("headline", {"pairs": n, "epl": args.epl})
-    result["roofline"]["traffic"] = pm.get("traffic") if pm else None
-    result["roofline"]["traffic_source"] = PMC_SOURCE if pm else why
-    result["roofline"]["valu"] = valu_roofline(eng, pm, why, avg_kernel_ms, n, "pair")
+    if args.dump_outputs:
+        result["dump_outputs"] = dump_outputs(eng, out, n, args.dump_outputs, rank, world)
+    if args.full:
+        # HBM traffic and the VALU counters of the same kernel from the committed PMC record
+        # (tools/pmc_target.sh -> profiles/pmc/headline.json), quoted only when the record was taken on
+        # THIS library binary (sha256 of libpvac_hip.so) and this batch shape; null plus the reason else
+        pm, why = pmc_record("headline", {"pairs": n, "epl": args.epl})
+        result["roofline"]["traffic"] = pm.get("traffic") if pm else None
+        result["roofline"]["traffic_source"] = PMC_SOURCE if pm else why
+        result["roofline"]["valu"] = valu_roofline(eng, pm, why, avg_kernel_ms, n, "pair")
 
-    # fresh-kernel pairs re-run on the general path during the timed steps (a key sum of 0 mod p:
-    # never for these uniform nonzero weights, so any redo here is a kernel defect costing time)
-    redo = eng.ct_mul_redo_count() - redo0
-    result["checks"] = self_checks(eng, args, A, B, out, nonces, n, first, seed, world, rank)
-    result["checks"]["fresh_redo"] = {"pairs_per_step": redo / args.steps, "ok": redo == 0}
-    result["checks"]["collective_backend"] = dist.get_backend() if dist_on else None
-    if rank == 0 and not args.no_cpu:
-        result["cpu_baseline"] = cpu_baseline(eng, A, B, out, n, args)
-    # the cfg-3 batch (~35 GB of inputs, outputs and nonces) is done with: release it so the side
-    # measurements (chains size their sub-batches from free HBM) run on an empty device
-    A = B = out = nonces = plan = None
-    placement.clear()
-    torch.cuda.synchronize(dev)
-    torch.cuda.empty_cache()
-    if rank == 0 and not args.no_extras:
-        try:
-            result["extras"] = extras(eng, args, world == 1 and not args.no_cpu)
-        except Exception as ex:   # side measurements must not hide the headline
-            result["extras"] = {"error": repr(ex)}
+        # fresh-kernel pairs re-run on the general path during the timed steps (a key sum of 0 mod p:
+        # never for these uniform nonzero weights, so any redo here is a kernel defect costing time)
+        redo = eng.ct_mul_redo_count() - redo0
+        result["checks"] = self_checks(eng, args, A, B, out, nonces, n, first, seed, world, rank)
+        result["checks"]["fresh_redo"] = {"pairs_per_step": redo / args.steps, "ok": redo == 0}
+        result["checks"]["collective_backend"] = dist.get_backend() if dist_on else None
+        if rank == 0 and not args.no_cpu:
+            result["cpu_baseline"] = cpu_baseline(eng, A, B, out, n, args)
+        # the cfg-3 batch (~35 GB of inputs, outputs and nonces) is done with: release it so the side
+        # measurements (chains size their sub-batches from free HBM) run on an empty device
+        A = B = out = nonces = plan = None
+        placement.clear()
+        torch.cuda.synchronize(dev)
+        torch.cuda.empty_cache()
+        if rank == 0 and not args.no_extras:
+            try:
+                result["extras"] = extras(eng, args, world == 1 and not args.no_cpu)
+            except Exception as ex:   # side measurements must not hide the headline
+                result["extras"] = {"error": repr(ex)}
     if rank == 0:
         print(json.dumps(result), flush=True)
     if dist_on:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SEED = 0x5EEDD0       # the sample of pairs --dump-outputs writes in full
+DUMP_PAIRS = 256
+DUMP_DIGESTS = 1 << 20     # per-pair digests of the first pairs of the shard (16 B each in the file)
+DUMP_BYTES = 48 * 10**6    # ceiling for the array data of all files of one rank
+
+
+def dump_outputs(eng, out, n, path, rank, world):
+    """--dump-outputs DIR: the batch the last timed step left in the caller's output arrays, as
+    DIR/<name>.npy in float64 (every file name carries `rank<r>_` in front at N > 1). The ciphers
+    hold u64 words, which float64 cannot carry, so every word is written as its two 32-bit halves
+    [low, high], both exact in float64: two builds agree on an array exactly or differ by >= 1.
+      pairs      (k,)      the pairs written in full: a fixed seeded sample of the shard's n pairs
+                           (DUMP_SEED; at most DUMP_PAIRS, fewer when their edges pass DUMP_BYTES)
+      l_cnt      (k,)      layers of each sampled output cipher
+      e_cnt      (k,)      edges of each sampled output cipher
+      layers     (sum l_cnt, 10)  the layer records, pair after pair, as ten 32-bit words each
+                           (rule, pa, pb, pad, then the halves of ztag, nonce_lo, nonce_hi)
+      meta, w_lo, w_hi  (sum e_cnt, 2)  the edges, pair after pair, in the order the engine emits
+      digest     (min(n, DUMP_DIGESTS), 2)  pvac_hip_batch_digest of every output cipher of the
+                           shard's first pairs: one word over all edges (meta, w) of a cipher
+    The inputs and nonces are keyed by (seed, global pair index) alone, so the same arguments give
+    the same arrays on every run."""
+    import numpy as np
+    import torch
+    dev = eng.device
+    os.makedirs(path, exist_ok=True)
+    halves = lambda a: np.stack([a & np.uint64(0xFFFFFFFF), a >> np.uint64(32)], axis=-1).astype(np.float64)
+    u = lambda t: t.cpu().numpy().view(np.uint64)
+    nd = min(n, DUMP_DIGESTS)
+    order = np.random.default_rng(DUMP_SEED).permutation(n)[:min(n, DUMP_PAIRS)]
+    oi = torch.from_numpy(order).to(dev)
+    cost = (80 * out.l_cnt[:n][oi] + 48 * out.e_cnt[:n][oi] + 24).cpu().numpy()
+    k = max(1, int(np.searchsorted(np.cumsum(cost), DUMP_BYTES - 16 * nd, side="right")))
+    pick = torch.from_numpy(np.sort(order[:k])).to(dev)
+
+    def rows(off, cnt):   # the used slots of the picked ciphers, in order
+        cnt = cnt[:n][pick].to(torch.int64)
+        start = off[:n][pick].to(torch.int64) - (torch.cumsum(cnt, 0) - cnt)
+        return torch.repeat_interleave(start, cnt) + torch.arange(int(cnt.sum().item()), device=dev), cnt
+
+    li, lc = rows(out.l_off, out.l_cnt)
+    ei, ec = rows(out.e_off, out.e_cnt)
+    arrays = {
+        "pairs": pick.cpu().numpy().astype(np.float64),
+        "l_cnt": lc.cpu().numpy().astype(np.float64),
+        "e_cnt": ec.cpu().numpy().astype(np.float64),
+        "layers": np.ascontiguousarray(out.layers[li].cpu().numpy()).view(np.uint32).reshape(-1, 10).astype(np.float64),
+        "meta": halves(u(out.meta[ei])),
+        "w_lo": halves(u(out.w_lo[ei])),
+        "w_hi": halves(u(out.w_hi[ei])),
+        "digest": halves(u(eng.digest(_head(out, nd)))),
+    }
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(path, prefix + name + ".npy"), a)
+    return {"files": [prefix + name + ".npy" for name in arrays], "dtype": "float64", "pairs_in_full": int(k),
+            "digests": int(nd), "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 FRESH_KERNEL = "k_ct_mul_fresh3"   # the fresh-pair kernel launch_ct_mul_fresh runs (k_mul_fresh.hip)

@@ -47,6 +47,14 @@ def test_spawn_refuses_more_gpus_than_visible():
     assert not [l for l in p.stdout.splitlines() if l.startswith("{")]
 
 
+def test_steps_below_one_are_refused():
+    """--steps sets the number of timed steps and ms_per_step is their mean: no steps, no line."""
+    p = _run(["--gpus", "1", "--steps", "0", "--warmup", "0"], {})
+    assert p.returncode == 2
+    assert "--steps must be at least 1" in p.stderr
+    assert not [l for l in p.stdout.splitlines() if l.startswith("{")]
+
+
 def test_launcher_ranks_sharing_a_device_fail():
     """Under an external launcher, two ranks that land on the same device stop with an error
     instead of reporting two GPUs."""

@@ -62,7 +62,7 @@ def test_bench_world2_shard_digests_equal_one_gpu():
     batch, rank 0 recomputes both ranks' pair windows from the global indices, the gsum invariant
     holds on every pair, and the gathered digest equals a one-rank run of the same 2 x 4096 pairs.
     The line counts ONE GPU for the two ranks."""
-    common = ["--steps", "1", "--warmup", "0", "--no-cpu", "--no-extras", "--check-window", "512"]
+    common = ["--full", "--steps", "1", "--warmup", "0", "--no-cpu", "--no-extras", "--check-window", "512"]
     two = _bench_json(["--gpus", "2", "--pairs", "4096"] + common, 2, shared=True)
     one = _bench_json(["--gpus", "1", "--pairs", "8192"] + common, 1)
     c2, c1 = two["checks"], one["checks"]
@@ -83,7 +83,7 @@ def test_bench_rccl_one_rank_collectives():
     and the result equals a run without any process group. (The 1-GPU pool cannot host two RCCL
     ranks on one device; the world-2 flow is covered over gloo above.)"""
     from test_shard_dist import _free_port
-    common = ["--gpus", "1", "--pairs", "4096", "--steps", "1", "--warmup", "0", "--no-cpu", "--no-extras",
+    common = ["--gpus", "1", "--pairs", "4096", "--full", "--steps", "1", "--warmup", "0", "--no-cpu", "--no-extras",
               "--check-window", "512"]
     rccl = _bench_json(common, 1, _free_port(), backend="nccl", launcher=True)
     plain = _bench_json(common, 1)
@@ -93,6 +93,49 @@ def test_bench_rccl_one_rank_collectives():
     assert c["result_gather"]["match"]   # shard.gather_batch over RCCL (one rank)
     assert c["global_digest"] == c0["global_digest"]
     assert c["global_output_edges"] == c0["global_output_edges"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_last_step(tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` line carries the headline and nothing that
+    takes a run of its own (checks, baselines and side measurements wait for --full), and
+    `--dump-outputs DIR` writes the batch the last timed step computed: float64 files whose 32-bit
+    halves rejoin to exactly the engine's own ct_mul of the same seeded pairs (every sampled
+    cipher's layers and edges in emit order, and the digest of every output cipher)."""
+    import json
+    from pvac_hfhe_cppbyv_amd import Engine
+    n, seed = 2048, 0x5EED0003
+    p = _bench_run(["--gpus", "1", "--pairs", str(n), "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)], 1)
+    assert p.returncode == 0, p.stderr[-3000:]
+    js = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(js) == 1, p.stdout[-3000:]
+    line = json.loads(js[0])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["full"] is False
+    assert abs(line["value"] - n / (line["ms_per_step"] / 1000.0)) <= 1e-6 * line["value"]
+    assert line["unit"] == "ct_mul/s" and line["higher_is_better"] is True and line["dtype"] == "u64" and line["metric"]
+    assert "checks" not in line and "extras" not in line and line["cpu_baseline"] is None
+    assert "valu" not in line["roofline"]
+    dump = line["dump_outputs"]
+    d = {f[:-len(".npy")]: np.load(tmp_path / f) for f in dump["files"]}
+    assert set(d) == {"pairs", "l_cnt", "e_cnt", "layers", "meta", "w_lo", "w_hi", "digest"}
+    assert all(a.dtype == np.float64 for a in d.values())
+    assert sum(a.nbytes for a in d.values()) == dump["bytes"] <= 64 * 10**6
+
+    eng = Engine(device=0, canon_tag=seed)
+    A, B = eng.gen_fresh(n, seed, 20), eng.gen_fresh(n, seed + 1, 20)
+    Cb, plan = eng.ct_mul_plan(A, B)
+    nonces = eng.fill_nonces(A, B, Cb, plan, seed + 2)
+    out = eng.ct_mul(A, B, nonces=nonces, C_=Cb, plan=plan)
+    join = lambda a: a[:, 0].astype(np.uint64) | (a[:, 1].astype(np.uint64) << np.uint64(32))
+    assert np.array_equal(join(d["digest"]), eng.digest(out).cpu().numpy().view(np.uint64))
+    pairs = d["pairs"].astype(np.int64)
+    assert len(pairs) == 256 and np.all(np.diff(pairs) > 0) and 0 <= pairs[0] and pairs[-1] < n
+    host = out.to_host()
+    got = [host[i] for i in pairs]
+    assert np.array_equal(d["l_cnt"], [c.nL for c in got]) and np.array_equal(d["e_cnt"], [c.nE for c in got])
+    lay = np.concatenate([c.layers for c in got])
+    assert np.array_equal(d["layers"], lay.view(np.uint32).reshape(-1, 10))
+    for name in ("meta", "w_lo", "w_hi"):
+        assert np.array_equal(join(d[name]), np.concatenate([getattr(c, name) for c in got])), name
 
 
 def test_bench_gpus2_on_one_gpu_fails_loudly():

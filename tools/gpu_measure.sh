@@ -3,7 +3,7 @@
 # script stopping at the first failure:
 #   1. the GPU test suite;
 #   2. the per-opcode issue probe (tools/issue_probe.py);
-#   3. the driver's bench line (bench.py defaults) and a kernel-trace summary of the headline command;
+#   3. the complete bench line (bench.py --full) and a kernel-trace summary of the headline command;
 #   4. PMC records stamped with this library's sha256 (tools/pmc_target.sh): headline, sigma, chain.
 # Output: gpurun_out/<tag>/ (copy what is judged into profiles/rNN/ and profiles/pmc/).
 # Usage: bash tools/gpu_measure.sh <tag> [steps...]   steps: tests probe bench trace pmc (default all)
@@ -26,7 +26,7 @@ if has probe; then
   timeout -k 10 300 python3 tools/issue_probe.py > "$OUT/issue_probe.json" || exit 1
 fi
 if has bench; then
-  timeout -k 10 900 python3 bench.py > "$OUT/bench.log" 2>&1 || { tail -5 "$OUT/bench.log"; exit 1; }
+  timeout -k 10 900 python3 bench.py --full > "$OUT/bench.log" 2>&1 || { tail -5 "$OUT/bench.log"; exit 1; }
   grep '^{' "$OUT/bench.log" | cut -c1-400
 fi
 if has trace; then

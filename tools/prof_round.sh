@@ -15,5 +15,5 @@ bash "$ROOT/tools/prof_pmc.sh" k_ct_mul_fresh > "$OUT/pmc.log" 2>&1 || exit $?
 cp "$ROOT/gpurun_out/pmc/summary.json" "$OUT/pmc_summary.json"
 cp "$ROOT/gpurun_out/pmc/pmc_ct_mul_fresh.json" "$OUT/pmc_ct_mul_fresh.json"
 echo "pmc ok"
-timeout -k 10 600 python3 "$ROOT/bench.py" > "$OUT/bench_default.log" 2>&1 || exit $?
+timeout -k 10 600 python3 "$ROOT/bench.py" --full > "$OUT/bench_default.log" 2>&1 || exit $?
 tail -1 "$OUT/bench_default.log"
