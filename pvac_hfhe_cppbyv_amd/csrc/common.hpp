@@ -331,6 +331,7 @@ struct mul_large_args {
     uint32_t lds_task;           // k_large_products_la: bytes of LDS below its staged B layers (set at launch)
     uint32_t la_per_wg;          // k_large_products_la: A layers per workgroup (max_la_wg = ceil(|A.L| / it))
     uint32_t la_xcd;             // k_large_products_la: 1 = all workgroups of a pair on one XCD (grid y padded to 8)
+                                 // (the host always passes 0; the field goes with a measured change to that kernel)
     uint32_t any_dyn;            // some pair has dynamic bucket chains (k_large_link runs)
     uint32_t all_iblk;           // every pair is iblk (rank / order / write on reduced grids)
     uint32_t any_direct;         // some pair is direct (large_desc::direct): the direct kernels run
@@ -351,7 +352,7 @@ struct mul_large_args {
     // over all, max_la_wg = ceil(|A.L| / kLaPerWG) over the A-layer-major class)
     uint64_t max_S, max_zero, max_tasks, max_capE, max_lay, max_tasks_all, max_la_wg, max_nA;
 };
-// k_large_products_la: A layers per workgroup (default; PVAC_LA_PER_WG); pairs with at most
+// k_large_products_la: A layers per workgroup; pairs with at most
 // kLaMaxLB B layers take it
 constexpr uint32_t kLaPerWG = 8;
 constexpr uint32_t kLaMaxLB = 4;

@@ -12,50 +12,22 @@ namespace {
 
 // Streaming (non-temporal) loads and stores, 4 vectors per lane: 6.10-6.25 TB/s against 5.50-5.59
 // with cached accesses and 2 vectors (cfg 2's 2^24-element add / mul, profiles/r06/ab/fp_ab.log)
-#ifndef PVAC_FP_UNROLL   // A/B builds only
-#define PVAC_FP_UNROLL 4
-#endif
-#ifndef PVAC_FP_NT   // A/B builds only
-#define PVAC_FP_NT 1
-#endif
 constexpr int kFpBlock = 256;
-constexpr int kFpUnroll = PVAC_FP_UNROLL;
+constexpr int kFpUnroll = 4;
 
 typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
-#ifndef PVAC_SCALE_NT   // A/B builds only: k_ct_scale's weights read and written non-temporally
-#define PVAC_SCALE_NT 1
-#endif
-__device__ __forceinline__ uint64_t ld_stream64(const uint64_t* p) {
-#if PVAC_SCALE_NT
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
-__device__ __forceinline__ void st_stream64(uint64_t* p, uint64_t v) {
-#if PVAC_SCALE_NT
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
+// (k_ct_scale's weights are read and written non-temporally too)
+__device__ __forceinline__ uint64_t ld_stream64(const uint64_t* p) { return __builtin_nontemporal_load(p); }
+__device__ __forceinline__ void st_stream64(uint64_t* p, uint64_t v) { __builtin_nontemporal_store(v, p); }
 __device__ __forceinline__ ulonglong2 ld_stream(const ulonglong2* p) {
-#if PVAC_FP_NT
     const u64x2_t v = __builtin_nontemporal_load((const u64x2_t*)p);
     return make_ulonglong2(v.x, v.y);
-#else
-    return *p;
-#endif
 }
 __device__ __forceinline__ void st_stream(ulonglong2* p, const ulonglong2& v) {
-#if PVAC_FP_NT
     u64x2_t w;
     w.x = v.x;
     w.y = v.y;
     __builtin_nontemporal_store(w, (u64x2_t*)p);
-#else
-    *p = v;
-#endif
 }
 
 template <int OP>

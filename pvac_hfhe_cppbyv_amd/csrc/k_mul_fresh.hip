@@ -32,15 +32,17 @@
 
 namespace pvhip {
 
-// Diagnostic build only (make diag -> lib/libpvac_hip_diag.so): wave 0 of every workgroup
-// accumulates s_memtime deltas per phase into a debug array; never touches kernel outputs.
-#ifdef PVAC_CENSUS   // diagnostic build only: per-workgroup start / end s_memrealtime (100 MHz) + pairs done
+// Census build only (make census -> lib/libpvac_hip_census.so): per-workgroup start / end
+// s_memrealtime (100 MHz) + pairs done; never touches kernel outputs.
+#ifdef PVAC_CENSUS
 __device__ unsigned long long g_census[4096 * 4];
 extern "C" int pvac_hip_diag_census(unsigned long long* host, size_t n) {
     if (n > sizeof(g_census) / 8) n = sizeof(g_census) / 8;
     return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_census), n * 8) == hipSuccess ? 0 : -5;
 }
 #endif
+// Diagnostic build only (make diag -> lib/libpvac_hip_diag.so): wave 0 of every workgroup
+// accumulates s_memtime deltas per phase into a debug array; never touches kernel outputs.
 #ifdef PVAC_PHASE_STAMPS
 constexpr int kStampPhases = 18;
 __device__ unsigned long long g_fresh_stamps[4096 * kStampPhases];
@@ -52,11 +54,8 @@ static_assert(kFreshLayersMax <= 64, "layer masks are u64");
 static_assert(kFreshKeysMax <= 2048 && kFreshLayersMax <= 512, "writer entries pack slot, idx (11 bits each) and layer");
 
 // ---------------------------------------------------------------- layer records
-#ifndef PVAC_LAY_LANES   // A/B builds only
-#define PVAC_LAY_LANES 4
-#endif
 constexpr int kLayBlock = 256;
-constexpr int kLayLanes = PVAC_LAY_LANES;   // lanes per pair: output layers (and their SHA-256 ztags) split over them
+constexpr int kLayLanes = 4;   // lanes per pair: output layers (and their SHA-256 ztags) split over them
 
 __global__ __launch_bounds__(kLayBlock) void k_mul_layers_fresh(mul_fresh_args g) {
     const uint64_t pr = ((uint64_t)blockIdx.x * kLayBlock + threadIdx.x) / kLayLanes;
@@ -98,11 +97,7 @@ __global__ __launch_bounds__(kLayBlock) void k_mul_layers_fresh(mul_fresh_args g
         y.pad = 0;
         y.nonce_lo = g.nonces[2 * slot];
         y.nonce_hi = g.nonces[2 * slot + 1];
-#ifdef PVAC_EXP_NOZTAG   // timing experiment only: no SHA-256 (ztags wrong)
-        y.ztag = y.nonce_lo ^ g.canon_tag;
-#else
         y.ztag = layer_ztag(g.canon_tag, y.nonce_lo, y.nonce_hi);
-#endif
         g.C.layers[slot] = y;
     }
 }
@@ -205,9 +200,6 @@ struct fresh_pref {
     uint32_t rule, pa, pb;
 };
 
-#ifndef PVAC_F3_PF_WAVES   // A/B builds: 0 = every wave prefetches (round 4)
-#define PVAC_F3_PF_WAVES 1
-#endif
 __device__ __forceinline__ fresh_pref prefetch_pair(argp g, const fresh_hdr& h, const uint32_t* hw,
                                                     uint32_t t = threadIdx.x) {
     // every lane of a loading wave loads a valid address (a clamped index, or the argument block
@@ -216,9 +208,7 @@ __device__ __forceinline__ fresh_pref prefetch_pair(argp g, const fresh_hdr& h, 
     // they loaded. Waves past the pair's edges and layers (wave-uniform: 7 of 8 for 40-edge
     // ciphers) load nothing.
     const bool live = h.pr != kNoPair;
-#if PVAC_F3_PF_WAVES
     if ((t & ~63u) >= max(max(h.nA, h.nB), h.LA + h.LB)) return fresh_pref{};
-#endif
     using gp64 = const __attribute__((address_space(1))) uint64_t*;   // global: never a flat load
     using gpl = const __attribute__((address_space(1))) uint32_t*;
     const gp64 dummy = (gp64)(uint64_t)g;
@@ -370,19 +360,6 @@ __host__ __device__ inline fresh3_layout fresh3_lds(uint32_t ks, uint32_t prod, 
     return L;
 }
 
-#ifndef PVAC_U5
-#define PVAC_U5 2
-#endif
-#ifndef PVAC_REP_P1   // experiment builds repeat a phase (idempotent) to measure its cost
-#define PVAC_REP_P1 1
-#endif
-#ifndef PVAC_REP_P2
-#define PVAC_REP_P2 1
-#endif
-#ifndef PVAC_REP_P4
-#define PVAC_REP_P4 1
-#endif
-
 #ifdef PVAC_PHASE_STAMPS
 #define STAMP3(ph)                                                        \
     do {                                                                  \
@@ -414,26 +391,18 @@ __device__ __forceinline__ uint32_t opaque(uint32_t x) {
     return x;
 }
 
-#ifndef PVAC_F3_BS   // A/B builds only: workgroup size of k_ct_mul_fresh3
-#define PVAC_F3_BS 512
-#endif
-#ifndef PVAC_F3_WPE   // A/B builds only: waves per SIMD the kernel is compiled for (6: <= 80 VGPRs)
-#define PVAC_F3_WPE 6
-#endif
-#ifndef PVAC_F3_U     // A/B builds only: product rounds per thread kept in registers from P1 to P5
-#define PVAC_F3_U 4
-#endif
-constexpr uint32_t kF3Threads = PVAC_F3_BS;
+constexpr uint32_t kF3Threads = 512;   // workgroup size of k_ct_mul_fresh3
+constexpr int kF3WavesPerSimd = 6;     // waves per SIMD the kernel is compiled for (6: <= 80 VGPRs)
 template <int BS>
-__global__ __launch_bounds__(BS, PVAC_F3_WPE) void k_ct_mul_fresh3(const mul_fresh_args* __restrict__ gp, fresh3_layout Ls) {
+__global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul_fresh_args* __restrict__ gp, fresh3_layout Ls) {
     constexpr int KI = (kFreshKeysMax + BS - 1) / BS;    // key slots per thread (rebuild)
     // bins per thread: a bin holds 2 or 3 slots except when size-2 buckets are left without a
     // size-1 partner, so there are at most kFreshKeysMax / 2 bins
     constexpr int KR = (kFreshKeysMax / 2 + BS - 1) / BS;
     constexpr int NW = BS / 64;
-    constexpr int U = PVAC_F3_U;                         // product rounds per pass
+    constexpr int U = 4;                                 // product rounds per pass (P1's stay in registers for P5)
     constexpr uint32_t kT16 = 0xFFFFu;                   // no first-insert time
-    static_assert(BS % 64 == 0 && BS >= (int)kFreshEdgesMax && NW <= 16, "fresh geometry");
+    static_assert(BS % 64 == 0 && BS >= (int)kFreshEdgesMax && NW <= 16 && U % 2 == 0, "fresh geometry");
     static_assert(kFreshProdMax <= 16u * 256u, "16 scan segments of 256 product times");
     argp gq = launder((uint64_t)gp);
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -668,7 +637,6 @@ __global__ __launch_bounds__(BS, PVAC_F3_WPE) void k_ct_mul_fresh3(const mul_fre
         uint32_t prod[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) prod[u] = ~0u;
-        for (int rep_ = 0; rep_ < PVAC_REP_P1; ++rep_) {   // experiment builds only (tools/exp_fresh3.py)
         {
             const uint32_t tid = opaque(threadIdx.x);
             for (uint32_t t0 = tid; t0 < n; t0 += U * BS) {
@@ -690,7 +658,6 @@ __global__ __launch_bounds__(BS, PVAC_F3_WPE) void k_ct_mul_fresh3(const mul_fre
                 }
             }
         }
-        }
         STAMP3_SYNC(1);
         if (wave == NW - 1 && lane < 16) misc[F3_HDR + lane] = hv;   // its load has had P1 to land
         __syncthreads();
@@ -704,14 +671,6 @@ __global__ __launch_bounds__(BS, PVAC_F3_WPE) void k_ct_mul_fresh3(const mul_fre
         //      bits of each slot, its bucket's first-insert time t_bkt, its rank in the bucket
         //      (edges of later keys) and the bucket's edge count G[t_bkt]
         uint32_t ordA[KR], ordB[KR];   // t_bkt of slots 0, 1 | t_bkt of slot 2, rank 3 bits x 3, emit 2 bits x 3
-#if PVAC_REP_P2 == 0   // experiment builds: no P2 (no emits, every bucket time "none")
-#pragma unroll
-        for (int k = 0; k < KR; ++k) {
-            ordA[k] = kT16 | (kT16 << 16);
-            ordB[k] = kT16;
-        }
-#endif
-        for (int rep_ = 0; rep_ < PVAC_REP_P2; ++rep_) {   // experiment builds only (tools/exp_fresh3.py)
         {
             auto cells = [&](uint64_t x, uint32_t& t, uint32_t& e) {
                 const uint32_t x0 = (uint32_t)x & kT16, x1 = (uint32_t)(x >> 32) & kT16;
@@ -761,7 +720,6 @@ __global__ __launch_bounds__(BS, PVAC_F3_WPE) void k_ct_mul_fresh3(const mul_fre
                 ordA[k] = tb0 | (tb1 << 16);
                 ordB[k] = tb2 | (wi0 << 16) | (wi1 << 19) | (wi2 << 22) | (e0 << 25) | (e1 << 27) | (e2 << 29);
             }
-        }
         }
         STAMP3_SYNC(3);
         __syncthreads();
@@ -849,7 +807,6 @@ __global__ __launch_bounds__(BS, PVAC_F3_WPE) void k_ct_mul_fresh3(const mul_fre
         // general path produces it (redo); this kernel emits the reference hash order only
         const bool canonical = (gq->flags & PVAC_MUL_ORDER_CANONICAL) != 0 || total > gq->edge_budget;
         const uint64_t ceo = cur.ceo;
-        for (int rep_ = 0; rep_ < PVAC_REP_P4; ++rep_) {   // experiment builds only (tools/exp_fresh3.py)
         {
             // 32-bit LDS byte offsets (no 64-bit address arithmetic): a cell word's low half, limb 2
             // of a position
@@ -920,7 +877,6 @@ __global__ __launch_bounds__(BS, PVAC_F3_WPE) void k_ct_mul_fresh3(const mul_fre
                 }
             }
         }
-        }
         const uint64_t keep = all_lp ? (Lc >= 64 ? ~0ull : ((1ull << Lc) - 1ull)) : *(const uint64_t*)(misc + F3_KEEP);
         const bool ident = all_lp || misc[F3_IDENT] != 0;
         if (!ident && wave == 1) {   // compact the identity-placed layer records in place
@@ -955,17 +911,11 @@ __global__ __launch_bounds__(BS, PVAC_F3_WPE) void k_ct_mul_fresh3(const mul_fre
 
         M3(5);
         // ---- P5: products into the limb accumulators of their emit positions
-#ifndef PVAC_EXP_SKIP_P5   // experiment builds only: no products (outputs wrong; the phase's cost)
         {
             const uint32_t tid = opaque(threadIdx.x);
             auto accumulate = [&](const ulonglong2& x, const ulonglong2& y, uint32_t p) {
                 uint64_t x0, x1, l0, l1, l2;
-#ifdef PVAC_EXP_NOMUL3
-                x0 = x.x ^ y.x;
-                x1 = (x.y ^ y.y) & 0x7FFFFFFFFFFFFFFFull;
-#else
                 fp_mul_fold1(fp{x.x, x.y}, fp{y.x, y.y}, x0, x1);
-#endif
                 fp_split3_44(x0, x1, l0, l1, l2);
                 unsigned long long* q = lim + 3u * p;
                 atomicAdd(q, (unsigned long long)l0);
@@ -980,7 +930,6 @@ __global__ __launch_bounds__(BS, PVAC_F3_WPE) void k_ct_mul_fresh3(const mul_fre
                 uint32_t p[2];
 #pragma unroll
                 for (int v = 0; v < 2; ++v) {
-                    if (u0 + v >= U) break;   // odd U (A/B builds)
                     const uint32_t pk = prod[u0 + v] == ~0u ? 0u : prod[u0 + v];
                     x[v] = a_w[pk & 0xFFu];
                     y[v] = b_w[(pk >> 8) & 0xFFu];
@@ -988,7 +937,7 @@ __global__ __launch_bounds__(BS, PVAC_F3_WPE) void k_ct_mul_fresh3(const mul_fre
                 }
 #pragma unroll
                 for (int v = 0; v < 2; ++v)
-                    if (u0 + v < U && prod[u0 + v] != ~0u) accumulate(x[v], y[v], p[v]);
+                    if (prod[u0 + v] != ~0u) accumulate(x[v], y[v], p[v]);
             }
             // further passes (n > U * BS): recompute
             for (uint32_t t = tid + U * BS; t < n; t += BS) {
@@ -999,7 +948,6 @@ __global__ __launch_bounds__(BS, PVAC_F3_WPE) void k_ct_mul_fresh3(const mul_fre
                 accumulate(x, y, p);
             }
         }
-#endif
         STAMP3_SYNC(9);
         __syncthreads();
         STAMP3(10);
@@ -1028,11 +976,7 @@ __global__ __launch_bounds__(BS, PVAC_F3_WPE) void k_ct_mul_fresh3(const mul_fre
             const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(cm, 0, 0x7FFFFFF8, 0x00020000);
             const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc(cl, 0, 0x7FFFFFF8, 0x00020000);
             const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc(chh, 0, 0x7FFFFFF8, 0x00020000);
-#ifdef PVAC_EXP_SKIP_W   // experiment builds only: no writer (outputs wrong; the phase's cost)
-            for (uint32_t p = tid; p < 0u; p += BS - 64) {
-#else
             for (uint32_t p = tid; p < total && wave != NW - 1; p += BS - 64) {
-#endif
                 unsigned long long* q = lim + 3u * p;
                 const uint64_t l0 = q[0], l1 = q[1], l2c = q[2];
                 q[0] = z64;
@@ -1135,10 +1079,7 @@ hipError_t launch_ct_mul_fresh(const mul_fresh_args& a, const mul_fresh_args* ar
     // the API counts LDS in 128-byte steps; measured residency (tools/res_probe.hip) follows
     // 2 KiB granules: 53,248 B gives 3 workgroups per CU, 53,888 B only 2
     const int lds_fit = (int)((160u * 1024u) / ((L.total + 2047u) & ~2047u));
-    int per_cu = std::min(std::min(occ_blocks, lds_fit), 3);
-#ifdef PVAC_FRESH_PER_CU   // probe builds only (tools/percu_probe.sh): fewer resident workgroups per CU
-    per_cu = std::max(1, std::min(per_cu, (int)PVAC_FRESH_PER_CU));
-#endif
+    const int per_cu = std::min(std::min(occ_blocks, lds_fit), 3);
     uint64_t blocks = (uint64_t)num_cus * per_cu;
     if (blocks > a.A.n) blocks = a.A.n;
     hipLaunchKernelGGL((k_ct_mul_fresh3<kF3Threads>), dim3((unsigned)blocks), dim3(kF3Threads), L.total, st,

@@ -118,10 +118,7 @@ __device__ __forceinline__ bool iblk_dead(const uint32_t* S, const large_desc& d
 // One workgroup per pair: validates edges (layer < |L|, idx < B, ch <= 1), buckets edge ids
 // by layer (any order inside a layer: first-insert times are minima, not positions) and
 // lists the non-empty layers of both sides.
-#ifndef PVAC_LIST_REG_ROUNDS   // rounds of 4 x kLBig A edges whose pass 2 reads registers
-#define PVAC_LIST_REG_ROUNDS 8
-#endif
-constexpr uint32_t kListRegRounds = PVAC_LIST_REG_ROUNDS;
+constexpr uint32_t kListRegRounds = 8;   // rounds of 4 x kLBig A edges whose pass 2 reads registers
 static_assert(kLargeLayersMax <= (1u << 15), "k_large_lists packs a layer in 15 bits");
 __global__ __launch_bounds__(kLBig) void k_large_lists(mul_large_args g) {
     extern __shared__ __attribute__((aligned(16))) uint32_t hist[];   // [LA + LB] counts, then cursors
@@ -321,12 +318,6 @@ constexpr uint64_t kDigC = 0x8080808080808080ull;  // 128 in every byte
 #else
 #define MXMARK(ph) do {} while (0)
 #endif
-#ifndef PVAC_EXP_IBREP   // experiment builds only: the per-A-edge passes run this many times (same result)
-#define PVAC_EXP_IBREP 1
-#endif
-#ifndef PVAC_EXP_MXREP   // experiment builds only: the MFMA loop run this many times (same result)
-#define PVAC_EXP_MXREP 1
-#endif
 
 // a loaded value kept in a VGPR until here: a uniform load is otherwise moved to an SGPR right
 // after it is issued, and that readfirstlane waits for every load in flight
@@ -364,17 +355,10 @@ __device__ __forceinline__ void fp_digits8(const fp& v, uint64_t& dl, uint64_t& 
 // 32-bit words h and 2 + h of the row's value: ga, gb (|g| < 2^48.1).
 // acc + (int64) x * m in one v_mad_i64_i32 (sign extension, shift and 64-bit add: the compiler's
 // form of a power-of-two multiple is a sign-extending shift plus a 64-bit shift-add per term)
-#ifndef PVAC_MX_MAD
-#define PVAC_MX_MAD 1
-#endif
 __device__ __forceinline__ int64_t mad_i64_i32(int32_t x, uint32_t m, int64_t acc) {
-#if PVAC_MX_MAD
     int64_t r;
     asm volatile("v_mad_i64_i32 %0, vcc, %1, %2, %3" : "=v"(r) : "v"(x), "s"(m), "v"(acc) : "vcc");
     return r;
-#else
-    return acc + (int64_t)x * (int64_t)m;
-#endif
 }
 __device__ __forceinline__ void mx_groups(const mx_v16& c, int64_t& ga, int64_t& gb) {
     int32_t d[8];
@@ -542,26 +526,16 @@ __device__ bool mx_blocks_n(const uint8_t* lds, const uint4* prec, const uint4* 
         const uint32_t rr = live ? r : 0u;
         mx_v16 aP{}, aM{};
         uint32_t tmin = kInf;
-        for (int rep_ = 0; rep_ < PVAC_EXP_MXREP; ++rep_) {   // experiment builds repeat the loop
-            uint32_t rq = rr;
-            asm volatile("" : "+v"(rq));
-            if (rep_) {   // keep the previous repetition live: add x - y where x == y at run time
-                int zp = aP[0], zm = aM[0];
-                asm volatile("" : "+v"(zp), "+v"(zm));
-                tmin += (uint32_t)(zp - aP[0]) + (uint32_t)(zm - aM[0]);
-            }
-            aP = mx_v16{};
-            aM = mx_v16{};
-            tmin = min(tmin, kInf);
+        uint32_t rq = rr;   // opaque copy: without it the k-steps' table reads are scheduled differently
+        asm volatile("" : "+v"(rq));   // (the measured code has it)
 #pragma unroll
-            for (int s = 0; s < NKS; ++s) {
-                const uint4 in = pinf[2u * (uint32_t)s + h];
-                const uint4 dp = dig[in.x + rq], dm = dig[in.y + rq];
-                const uint32_t tp = tt[in.x + rq], tm = tt[in.y + rq];
-                aP = __builtin_amdgcn_mfma_i32_32x32x32_i8(frag[s], mx_v4{(int)dp.x, (int)dp.y, (int)dp.z, (int)dp.w}, aP, 0, 0, 0);
-                aM = __builtin_amdgcn_mfma_i32_32x32x32_i8(frag[s], mx_v4{(int)dm.x, (int)dm.y, (int)dm.z, (int)dm.w}, aM, 0, 0, 0);
-                tmin = min(tmin, min(__builtin_elementwise_add_sat(tp, in.z), __builtin_elementwise_add_sat(tm, in.z)));
-            }
+        for (int s = 0; s < NKS; ++s) {
+            const uint4 in = pinf[2u * (uint32_t)s + h];
+            const uint4 dp = dig[in.x + rq], dm = dig[in.y + rq];
+            const uint32_t tp = tt[in.x + rq], tm = tt[in.y + rq];
+            aP = __builtin_amdgcn_mfma_i32_32x32x32_i8(frag[s], mx_v4{(int)dp.x, (int)dp.y, (int)dp.z, (int)dp.w}, aP, 0, 0, 0);
+            aM = __builtin_amdgcn_mfma_i32_32x32x32_i8(frag[s], mx_v4{(int)dm.x, (int)dm.y, (int)dm.z, (int)dm.w}, aM, 0, 0, 0);
+            tmin = min(tmin, min(__builtin_elementwise_add_sat(tp, in.z), __builtin_elementwise_add_sat(tm, in.z)));
         }
         MXMARK(3);
         // half 0 folds row r's P sum, half 1 its M sum; each needs the other half's two words
@@ -821,7 +795,7 @@ __device__ void run_task(const mul_large_args& g, const large_desc& d, uint32_t 
 }
 
 // one workgroup per task (la, lb): pairs with many B layers (squares)
-template <int BS, bool MX>
+template <int BS>
 __global__ __launch_bounds__(BS) void k_large_products(mul_large_args g) {
     extern __shared__ __attribute__((aligned(16))) uint8_t plds[];
     const large_desc& d = g.desc[g.sel[g.n_la + blockIdx.y]];
@@ -832,7 +806,7 @@ __global__ __launch_bounds__(BS) void k_large_products(mul_large_args g) {
     const uint32_t tl = blockIdx.x;
     const uint32_t la_i = tl / LB, lb_i = tl - la_i * LB;
     if (la_i >= cnt[0] || lb_i >= cnt[1]) return;
-    run_task<BS, MX>(g, d, S[d.o_neA + la_i], S[d.o_neB + lb_i], plds);
+    run_task<BS, true>(g, d, S[d.o_neA + la_i], S[d.o_neB + lb_i], plds);
 }
 
 // ---- per-A-edge emit order (iblk pairs) ---------------------------------------------------
@@ -1018,13 +992,11 @@ __device__ bool stage_tt(uint8_t* lds, uint32_t Bm, const layer_src& D, uint32_t
 // then iblk_layer's counts and masks; product-layer used flags for compact_layers. A layer the
 // matrix-core mode cannot take (duplicate edges, fewer than kLargeDenseMin edges) fails the pair
 // (cnt[kCntIFail]): k_large_scan_direct sends it to the host's redo.
-template <int BS>
 // resident workgroups per CU k_large_count_la is compiled for: 6 (<= 80 VGPRs, no spills) against
 // 5 (81 VGPRs unconstrained): cfg-4 chain 195 K against 188-190 K ct_mul/s on one stream; 7 spills
-#ifndef PVAC_CNT_MINB
-#define PVAC_CNT_MINB 6
-#endif
-__global__ __launch_bounds__(BS, PVAC_CNT_MINB) void k_large_count_la(mul_large_args g) {
+constexpr int kCntMinBlocks = 6;
+template <int BS>
+__global__ __launch_bounds__(BS, kCntMinBlocks) void k_large_count_la(mul_large_args g) {
     extern __shared__ __attribute__((aligned(16))) uint8_t plds[];
     const large_desc d = g.desc[g.sel[blockIdx.y]];   // registers (the kernel's stores could alias it)
     if (!d.direct) return;
@@ -1328,11 +1300,9 @@ __global__ __launch_bounds__(64) void k_large_direct_redo(mul_large_args g) {
 // Tasks the matrix-core mode does not take: sparse x sparse (and layers with duplicate edges) run
 // the scatter mode in place; dense tasks with a large sparse side (column mode, 33 KB of LDS) go to
 // a per-pair list for k_large_products_defer.
-#ifndef PVAC_LA_MINB   // resident workgroups per CU the A-layer-major kernel is compiled for
-#define PVAC_LA_MINB 4
-#endif
+constexpr int kLaMinBlocks = 4;   // resident workgroups per CU the A-layer-major kernel is compiled for
 template <int BS>
-__global__ __launch_bounds__(BS, PVAC_LA_MINB) void k_large_products_la(mul_large_args g) {
+__global__ __launch_bounds__(BS, kLaMinBlocks) void k_large_products_la(mul_large_args g) {
     extern __shared__ __attribute__((aligned(16))) uint8_t plds[];
     uint32_t py = blockIdx.y, px = blockIdx.x;
     if (g.la_xcd) {   // workgroups go to XCDs round-robin by linear id: XCD x takes pairs x, x + 8, ...
@@ -1392,9 +1362,6 @@ __global__ __launch_bounds__(BS, PVAC_LA_MINB) void k_large_products_la(mul_larg
             for (uint32_t k = 0; k < kLaMaxLB; ++k)
                 if (((okm >> k) & 1u) && na >= nbv[k]) mxm |= 1u << k;
         if (mxm) {
-#ifdef PVAC_EXP_STAGE2   // experiment builds only: the dense staging twice (same result)
-            mx_stage_dense<BS>(plds, Bm, srcA, nB);
-#endif
             if (mx_stage_dense<BS>(plds, Bm, srcA, nB)) {   // barriers inside (they also publish the B staging)
 #pragma unroll
                 for (uint32_t k = 0; k < kLaMaxLB; ++k) {
@@ -1430,9 +1397,8 @@ __global__ __launch_bounds__(BS, PVAC_LA_MINB) void k_large_products_la(mul_larg
             // (idx, ch) edges): count and rank per A edge; otherwise the pair falls back
             if (mxm == (1u << neB) - 1u) {
                 static_assert(kLaMaxLB == 4, "iblk_layer takes the B layers as a uint4");
-                for (int rep_ = 0; rep_ < PVAC_EXP_IBREP; ++rep_)   // experiment builds repeat it (idempotent)
-                    iblk_layer<BS>(plds, g, d, la, make_uint4(lbv[0], lbv[1], lbv[2], lbv[3]), neB, recs, S + d.o_icnt,
-                                   (ulonglong2*)(S + d.o_imask));
+                iblk_layer<BS>(plds, g, d, la, make_uint4(lbv[0], lbv[1], lbv[2], lbv[3]), neB, recs, S + d.o_icnt,
+                               (ulonglong2*)(S + d.o_imask));
             } else {
                 if (threadIdx.x == 0) atomicExch(&S[d.o_cnt + kCntIFail], 1u);
                 ib = false;
@@ -1527,9 +1493,8 @@ __device__ __forceinline__ void dir_stage_sparse(uint4* prec, uint4* pinf, uint3
 }
 
 // one task's products, each row's P (half 0) / M (half 1) sum into stg[(r) 2 + h]
-#ifndef PVAC_DIR_PINF_REG   // A/B builds: 1 = the k-steps' sparse-edge offsets held in registers for every block
-#define PVAC_DIR_PINF_REG 0   // (177 instead of 187 VALU per block, but 21 spill ops: 428-429 K against 430-431 K)
-#endif
+// (the k-steps' sparse-edge offsets are read from LDS per block: held in registers for every block they
+// cost 177 instead of 187 VALU per block, but 21 spill ops: 428-429 K against 430-431 K)
 template <int BS, int NKS>
 __device__ void dir_rows_n(const uint4* dig, const uint4* prec, const uint4* pinf, uint32_t Bm, ulonglong2* stg) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -1546,43 +1511,18 @@ __device__ void dir_rows_n(const uint4* dig, const uint4* prec, const uint4* pin
                             (int)__builtin_amdgcn_alignbyte(w3, w2, sh), (int)__builtin_amdgcn_alignbyte(w4, w3, sh)};
         }
     }
-#if PVAC_DIR_PINF_REG
-    // the k-steps' sparse-edge words, byte offsets into the digit table packed as
-    // (B - idx) 16 | (P table base) 16 << 16, held in registers for every block: the digit reads of a
-    // block depend on no LDS read of their own (the M table base is B 16 minus the P one)
-    uint32_t pk[NKS];
-#pragma unroll
-    for (int s = 0; s < NKS; ++s) {
-        const uint4 in = pinf[2u * (uint32_t)s + h];
-        pk[s] = (in.x << 4) | (in.y << 20);
-    }
-    const uint32_t B16 = Bm << 4;
-#endif
     const uint32_t nblk = (Bm + 31u) >> 5;
     for (uint32_t blk = wave; blk < nblk; blk += BS / 64) {
         const uint32_t r = blk * 32u + n;
         const bool live = r < Bm;
         const uint32_t rr = live ? r : 0u;
         mx_v16 aP{}, aM{};
-#if PVAC_DIR_PINF_REG
-        const uint32_t rr16 = rr << 4;
-        const uint8_t* dg = (const uint8_t*)dig;
-#pragma unroll
-        for (int s = 0; s < NKS; ++s) asm volatile("" : "+v"(pk[s]));   // unpacked per block: 10 registers, not 20
-#endif
 #pragma unroll
         for (int s = 0; s < NKS; ++s) {
-#if PVAC_DIR_PINF_REG
-            uint32_t x = rr16 + (pk[s] & 0xFFFFu);   // 16 ((r - idx) mod B)
-            x = min(x, x - B16);
-            const uint4 dp = *(const uint4*)(dg + x + (pk[s] >> 16));
-            const uint4 dm = *(const uint4*)(dg + (x + B16) - (pk[s] >> 16));
-#else
             const uint4 in = pinf[2u * (uint32_t)s + h];
             uint32_t x = rr + in.x;   // (r - idx) mod B
             x = min(x, x - Bm);
             const uint4 dp = dig[in.y + x], dm = dig[in.z + x];
-#endif
             aP = __builtin_amdgcn_mfma_i32_32x32x32_i8(frag[s], mx_v4{(int)dp.x, (int)dp.y, (int)dp.z, (int)dp.w}, aP, 0, 0, 0);
             aM = __builtin_amdgcn_mfma_i32_32x32x32_i8(frag[s], mx_v4{(int)dm.x, (int)dm.y, (int)dm.z, (int)dm.w}, aM, 0, 0, 0);
         }
@@ -1616,11 +1556,9 @@ __device__ void dir_rows(const uint4* dig, const uint4* prec, const uint4* pinf,
 // cache policy bits of the products kernel's record stores. Streaming (2) was measured against the
 // default (0) on the cfg-4 chain: HBM writes 84.4 against 70.8 GB per 4096 inputs (lines leave L2
 // before their neighbours' records fill them, then go out again), reads 47.2 against 58.5, time equal
-#ifndef PVAC_DIR_STORE_AUX
-#define PVAC_DIR_STORE_AUX 0
-#endif
+constexpr int kDirStoreAux = 0;
 template <int BS>
-__global__ __launch_bounds__(BS, PVAC_LA_MINB) void k_large_products_direct(mul_large_args g) {
+__global__ __launch_bounds__(BS, kLaMinBlocks) void k_large_products_direct(mul_large_args g) {
     extern __shared__ __attribute__((aligned(16))) uint8_t plds[];
     // a register copy of the descriptor: C's stores could alias it, so field reads through the
     // reference were reloaded from memory (a dependent round trip each) after every store
@@ -1763,13 +1701,13 @@ __global__ __launch_bounds__(BS, PVAC_LA_MINB) void k_large_products_direct(mul_
                     if (hp) {
                         const ulonglong2 w = stg[(kb * Bm + r) * 2u];
                         if ((w.x | w.y) == 0ull) cnt[kCntRedo] = 1u;   // a present cell whose products cancel
-                        __builtin_amdgcn_raw_buffer_store_b32(pos | r << 21, rmeta, (sbase + r) * 4u, 0, PVAC_DIR_STORE_AUX);
+                        __builtin_amdgcn_raw_buffer_store_b32(pos | r << 21, rmeta, (sbase + r) * 4u, 0, kDirStoreAux);
                     }
                     if (hm) {
                         const ulonglong2 w = stg[(kb * Bm + r) * 2u + 1u];
                         if ((w.x | w.y) == 0ull) cnt[kCntRedo] = 1u;
                         __builtin_amdgcn_raw_buffer_store_b32((pos + hp) | (Bm + r) << 21, rmeta, (sbase + Bm + r) * 4u, 0,
-                                                              PVAC_DIR_STORE_AUX);
+                                                              kDirStoreAux);
                     }
                 }
                 if (b0 + BS < nw) __syncthreads();   // the next round rewrites obase / oidx / omk
@@ -1787,10 +1725,10 @@ __global__ __launch_bounds__(BS, PVAC_LA_MINB) void k_large_products_direct(mul_
                     if (ptab_ok) {   // every cell is a key (the image is dense)
                         if ((w.x | w.y) == 0ull) cnt[kCntRedo] = 1u;   // a present cell whose products cancel
                         __builtin_amdgcn_raw_buffer_store_b32(ptab[k * 2u * Bm + c] | c << 21, rmeta, (sbase + c) * 4u, 0,
-                                                              PVAC_DIR_STORE_AUX);
+                                                              kDirStoreAux);
                     }
-                    __builtin_amdgcn_raw_buffer_store_b64(u2v{(uint32_t)w.x, (uint32_t)(w.x >> 32)}, rlo, bo, 0, PVAC_DIR_STORE_AUX);
-                    __builtin_amdgcn_raw_buffer_store_b64(u2v{(uint32_t)w.y, (uint32_t)(w.y >> 32)}, rhi, bo, 0, PVAC_DIR_STORE_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b64(u2v{(uint32_t)w.x, (uint32_t)(w.x >> 32)}, rlo, bo, 0, kDirStoreAux);
+                    __builtin_amdgcn_raw_buffer_store_b64(u2v{(uint32_t)w.y, (uint32_t)(w.y >> 32)}, rhi, bo, 0, kDirStoreAux);
                 }
             }
             DSTAMP(8);
@@ -1837,9 +1775,9 @@ __global__ __launch_bounds__(BS, PVAC_LA_MINB) void k_large_products_direct(mul_
                 const uint32_t pos = obase[l] + q;
                 const uint64_t mv = make_meta(lidk, r, ch);
                 const uint32_t bo = pos * 8u;   // < 2^31: the host caps a direct pair at 2^21 A edges
-                __builtin_amdgcn_raw_buffer_store_b64(u2v{(uint32_t)mv, (uint32_t)(mv >> 32)}, rmeta, bo, 0, PVAC_DIR_STORE_AUX);
-                __builtin_amdgcn_raw_buffer_store_b64(u2v{(uint32_t)w.x, (uint32_t)(w.x >> 32)}, rlo, bo, 0, PVAC_DIR_STORE_AUX);
-                __builtin_amdgcn_raw_buffer_store_b64(u2v{(uint32_t)w.y, (uint32_t)(w.y >> 32)}, rhi, bo, 0, PVAC_DIR_STORE_AUX);
+                __builtin_amdgcn_raw_buffer_store_b64(u2v{(uint32_t)mv, (uint32_t)(mv >> 32)}, rmeta, bo, 0, kDirStoreAux);
+                __builtin_amdgcn_raw_buffer_store_b64(u2v{(uint32_t)w.x, (uint32_t)(w.x >> 32)}, rlo, bo, 0, kDirStoreAux);
+                __builtin_amdgcn_raw_buffer_store_b64(u2v{(uint32_t)w.y, (uint32_t)(w.y >> 32)}, rhi, bo, 0, kDirStoreAux);
                 if (g.salt_pos) g.salt_pos[ceo + pos] = pos;
             }
             if (b0 + BS < nw) __syncthreads();   // the next round rewrites okey / obase
@@ -2515,7 +2453,6 @@ hipError_t launch_ct_mul_large(const mul_large_args& a, hipStream_t st) {
     hipLaunchKernelGGL(k_large_init, dim3(grid_x(a.max_zero > a.max_S ? a.max_zero : a.max_S, kLB * 4, 4096), nl),
                        dim3(kLB), 0, st, a);
     hipLaunchKernelGGL(k_large_lists, dim3(nl), dim3(kLBig), (size_t)a.max_lay * 4, st, a);
-#ifndef PVAC_LARGE_PRODUCTS_COL26
     if (a.any_direct && a.n_la && a.max_la_wg) {
         // direct pairs: presence counts, offsets, compact_layers, then products straight to C
         mul_large_args b = a;
@@ -2530,21 +2467,12 @@ hipError_t launch_ct_mul_large(const mul_large_args& a, hipStream_t st) {
         hipLaunchKernelGGL(k_large_direct_redo, dim3((nl + 63) / 64), dim3(64), 0, st, b);
         if (a.all_direct) return hipGetLastError();
     }
-#endif
     // products: the matrix-core dense mode in 4-wave workgroups (A-layer-major for pairs with few B
-    // layers, one task per workgroup for the rest). A/B builds with -DPVAC_LARGE_PRODUCTS_COL26 run
-    // the column-accumulator kernel of round 2 for every pair instead (never the shipped library).
-#ifdef PVAC_LARGE_PRODUCTS_COL26
-    {
-        mul_large_args b = a;
-        b.n_la = 0;
-        hipLaunchKernelGGL((k_large_products<kLP, false>), dim3((unsigned)a.max_tasks_all, nl), dim3(kLP), plds, st, b);
-    }
-#else
+    // layers, one task per workgroup for the rest)
     {
         const size_t lx = std::max<size_t>(plds, mx_lds_bytes(a.Bm) + kMxSparseBytes);
         if (nl > a.n_la && a.max_tasks)
-            hipLaunchKernelGGL((k_large_products<kLPX, true>), dim3((unsigned)a.max_tasks, nl - a.n_la), dim3(kLPX), lx, st, a);
+            hipLaunchKernelGGL((k_large_products<kLPX>), dim3((unsigned)a.max_tasks, nl - a.n_la), dim3(kLPX), lx, st, a);
         if (a.n_la && a.max_la_wg) {
             mul_large_args b = a;
             b.lds_task = mx_lds_bytes(a.Bm);   // the scatter mode (52 B per slot) fits below it
@@ -2554,7 +2482,6 @@ hipError_t launch_ct_mul_large(const mul_large_args& a, hipStream_t st) {
             hipLaunchKernelGGL((k_large_products_defer<kLPX>), dim3(kDeferWG, a.n_la), dim3(kLPX), plds, st, a);
         }
     }
-#endif
     hipLaunchKernelGGL(k_large_layers, dim3(nl), dim3(kLBig), (size_t)a.max_lay * 4, st, a);
     const unsigned gs = grid_x(a.max_S, kLB * 2, 4096);
     // a batch of iblk pairs runs rank / order / write only for the few that share buckets, need the

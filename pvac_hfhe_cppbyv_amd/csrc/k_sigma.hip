@@ -208,16 +208,8 @@ struct sig_args {
 // noise rows [2 kNoiseWords] u16 | midstates [32 edges][2 streams][8] u32
 // 6 blocks per CU (6 waves per SIMD): the compiler keeps the pass loop within 80 VGPRs without
 // spills instead of hoisting the whole SHA-256 message schedule (149 VGPRs, 3 waves per SIMD)
-#ifdef PVAC_EXP_SIG_MID16   // experiment builds only: 16-edge midstate batches, 7 workgroups per CU
-constexpr uint32_t kMidBatch = 16;
-constexpr int kSigMinBlocks = 7;
-#elif defined(PVAC_EXP_SIG_MINB5)   // experiment builds only: 5 workgroups per CU (96 VGPRs, no spills)
-constexpr uint32_t kMidBatch = 32;
-constexpr int kSigMinBlocks = 5;
-#else
 constexpr uint32_t kMidBatch = 32;   // edges whose block-0 midstates one compression per lane covers
 constexpr int kSigMinBlocks = 6;
-#endif
 // The delta path flips into four bank-interleaved copies of the image (word W of copy k at dword
 // 4 W + k of the 1024 words sigma | bmX | bmN, dead after the selection), copy k = lane & 3: the 8
 // lanes of a 32-lane ds_xor group that share a copy meet on 8 banks, instead of 32 lanes on 32
@@ -225,11 +217,8 @@ constexpr int kSigMinBlocks = 6;
 // (round 4: 35.2 -> 30.5 ms per 5.05 M edges, A/B in one process). The noise rows wait in
 // kNoiseWords after the columns and are flipped with them; the output word is the XOR of its copies.
 constexpr uint32_t kNoiseWords = 64;
-#ifdef PVAC_EXP_SIG_COPY8   // experiment builds only: eight image copies (copy = lane & 7)
-constexpr uint32_t kSigCopies = 8;
-#else
 constexpr uint32_t kSigCopies = 4;
-#endif
+static_assert(kSigCopies == 4, "the flips place word W of copy k at byte 16 W + 4 k");
 // words of the image region (sigma | bmX | bmN, and the delta path's copies)
 __host__ __device__ constexpr uint32_t sigma_img_words(uint32_t m_bits, uint32_t n_bits) {
     return m_bits / 32 + n_bits / 32 + m_bits / 32 > kSigCopies * (m_bits / 32) ? m_bits / 32 + n_bits / 32 + m_bits / 32
@@ -293,7 +282,7 @@ constexpr uint32_t kDeltaBytes = 208;   // 13 chunks of 16 increments; <= 8 brid
 template <int WV>
 __device__ __forceinline__ void flip_cols_delta(const uint8_t* tab, uint32_t c0, uint32_t c1) {
     constexpr uint32_t img = WV * kFastWaveWords * 4u;   // byte address of wave WV's image
-    uint32_t two = kSigCopies == 8 ? 5u : 4u, one = 1u;   // word W of copy k at byte 4 (copies W + k)
+    uint32_t two = 4u, one = 1u;   // word W of copy k at byte 4 (copies W + k)
     const uint32_t kofs = (threadIdx.x & (kSigCopies - 1u)) << 2;
     asm volatile("" : "+v"(two), "+v"(one));   // VGPR operands for the SDWA shifts
     auto word4 = [&](uint32_t& R, uint32_t w) {
@@ -317,33 +306,15 @@ __device__ __forceinline__ void flip_cols_delta(const uint8_t* tab, uint32_t c0,
         uint32_t R = 0;
         {
             uint4 v[8];
-#ifdef PVAC_EXP_SIG_DNOLOAD   // timing experiment: synthetic increments, no table reads (sigma wrong)
-#pragma unroll
-            for (int b = 0; b < 8; ++b) {
-                const uint32_t h = ((cc ? c1 : c0) * 0x9E3779B1u + b * 0x85EBCA77u);
-                v[b] = make_uint4(h & 0x3F3F3F3Fu, (h * 0xC2B2AE3Du) & 0x3F3F3F3Fu, (h * 0x27D4EB2Fu) & 0x3F3F3F3Fu,
-                                  (h * 0x165667B1u) & 0x3F3F3F3Fu);
-            }
-#else
 #pragma unroll
             for (int b = 0; b < 8; ++b) v[b] = rp[b];
-#endif
 #pragma unroll
             for (int b = 0; b < 8; ++b) { word4(R, v[b].x); word4(R, v[b].y); word4(R, v[b].z); word4(R, v[b].w); }
         }
         {
             uint4 v[5];
-#ifdef PVAC_EXP_SIG_DNOLOAD
-#pragma unroll
-            for (int b = 0; b < 5; ++b) {
-                const uint32_t h = ((cc ? c1 : c0) * 0x9E3779B1u + (b + 8) * 0x85EBCA77u);
-                v[b] = make_uint4(h & 0x3F3F3F3Fu, (h * 0xC2B2AE3Du) & 0x3F3F3F3Fu, (h * 0x27D4EB2Fu) & 0x3F3F3F3Fu,
-                                  (h * 0x165667B1u) & 0x3F3F3F3Fu);
-            }
-#else
 #pragma unroll
             for (int b = 0; b < 5; ++b) v[b] = rp[8 + b];
-#endif
 #pragma unroll
             for (int b = 0; b < 5; ++b) { word4(R, v[b].x); word4(R, v[b].y); word4(R, v[b].z); word4(R, v[b].w); }
         }
@@ -499,20 +470,9 @@ __global__ __launch_bounds__(kSigBlock, kSigMinBlocks) void k_sigma(sig_args a) 
             // different groups never contend for a word. Copy 0 already holds the noise bits.
             const uint32_t W = a.width;
             if (a.rows_delta && lds_at0) {   // host-checked: default Params, kFastWaveWords per wave
-#if defined(PVAC_EXP_SIG_PRIO0)
-                __builtin_amdgcn_s_setprio(0);
-#elif defined(PVAC_EXP_SIG_PRIO1)
-                __builtin_amdgcn_s_setprio(1);
-#elif defined(PVAC_EXP_SIG_PRIO3)
-                __builtin_amdgcn_s_setprio(3);
-#else
                 __builtin_amdgcn_s_setprio(2);   // LDS-atomic phase ahead of other waves' SHA-256
-#endif
                 const uint32_t c0 = cols[lane], c1 = cols[lane + 64];   // x_col_wt == 128
                 for (uint32_t w4 = lane; w4 < (bx32 + bn32) / 4u; w4 += 64) ((uint4*)bmX)[w4] = make_uint4(0, 0, 0, 0);
-#ifdef PVAC_EXP_SIG_NOEXP   // timing experiment: no column expansion (sigma wrong)
-                if (a.width == 0x7FFFFFFFu)
-#endif
                 switch (__builtin_amdgcn_readfirstlane(wave)) {
                     case 0: flip_cols_delta<0>(a.rows_delta, c0, c1); break;
                     case 1: flip_cols_delta<1>(a.rows_delta, c0, c1); break;
@@ -523,7 +483,7 @@ __global__ __launch_bounds__(kSigBlock, kSigMinBlocks) void k_sigma(sig_args a) 
                     const uint32_t kofs = ((uint32_t)lane & (kSigCopies - 1u)) << 2;
                     for (uint32_t q = (uint32_t)lane; q < a.err_wt; q += 64) {
                         const uint32_t r = nrows[q];
-                        atomicXor((uint32_t*)((uint8_t*)sig + (((r >> 5) << (kSigCopies == 8 ? 5 : 4)) | kofs)),
+                        atomicXor((uint32_t*)((uint8_t*)sig + (((r >> 5) << 4) | kofs)),
                                   1u << (r & 31u));
                     }
                 }
@@ -557,9 +517,6 @@ __global__ __launch_bounds__(kSigBlock, kSigMinBlocks) void k_sigma(sig_args a) 
                 const uint32_t c0 = (uint32_t)lane < a.x_col_wt ? cols[lane] : 0u;
                 const uint32_t c1 = (uint32_t)lane + 64u < a.x_col_wt ? cols[lane + 64] : 0u;
                 for (uint32_t w4 = lane; w4 < (bx32 + bn32) / 4u; w4 += 64) ((uint4*)bmX)[w4] = make_uint4(0, 0, 0, 0);
-#ifdef PVAC_EXP_SIG_NOEXP   // timing experiment: no column expansion (sigma wrong)
-                if (a.width == 0x7FFFFFFFu)
-#endif
                 switch (__builtin_amdgcn_readfirstlane(wave)) {
                     case 0: flip_cols_fast<0>(a.rows_fast, W, c0, c1, a.x_col_wt, lane); break;
                     case 1: flip_cols_fast<1>(a.rows_fast, W, c0, c1, a.x_col_wt, lane); break;
@@ -635,9 +592,6 @@ __global__ __launch_bounds__(kSigBlock, kSigMinBlocks) void k_sigma(sig_args a) 
             const uint32_t grp = split ? (uint32_t)lane >> 4 : 0u;
             uint32_t* img = sig + 256u * grp;
             const uint32_t skew = 16u * grp;
-#ifdef PVAC_EXP_SIG_NOXOR
-            if (a.width == 0x7FFFFFFFu)   // timing experiment: no column expansion at all
-#endif
             for (uint32_t c = lane; c < a.x_col_wt; c += 64) {
                 const uint32_t col = cols[c];
                 const uint32_t cnt = a.counts[col];
@@ -655,15 +609,10 @@ __global__ __launch_bounds__(kSigBlock, kSigMinBlocks) void k_sigma(sig_args a) 
                         const uint32_t kb = k8 + 8 * b;
                         const uint32_t rr[8] = {v[b].x & 0xFFFFu, v[b].x >> 16, v[b].y & 0xFFFFu, v[b].y >> 16,
                                                 v[b].z & 0xFFFFu, v[b].z >> 16, v[b].w & 0xFFFFu, v[b].w >> 16};
-#ifdef PVAC_EXP_SIG_NOLDSXOR
-                        // timing experiment: rows read, no LDS atomics
-                        if ((rr[0] ^ rr[3] ^ rr[7]) == 0xFFFFFFFFu) sig[0] = rr[1];
-#else
 #pragma unroll
                         for (int j = 0; j < 8; ++j)
                             if (kb + j < cnt)
                                 atomicXor(&img[split ? ((rr[j] >> 5) + skew) & 255u : rr[j] >> 5], 1u << (rr[j] & 31));
-#endif
                     }
                 }
             }
@@ -972,11 +921,6 @@ hipError_t launch_sigma(const sigma_tables& T, const pvac_hip_params& prm, const
         const std::string pv(v);
         path = pv == "u16" ? 1 : pv == "copies" ? 2 : pv == "generic" ? 3 : 0;
     }
-#if defined(PVAC_EXP_SIG_OLD)   // A/B builds only (make exp-sig)
-    path = 2;
-#elif defined(PVAC_EXP_SIG_U16)
-    path = 1;
-#endif
     const bool fast_ok = prm.m_bits == 8192 && prm.x_col_wt == 128 && T.full &&
                          sigma_wave_words(prm.m_bits, prm.n_bits, prm.x_col_wt) == kFastWaveWords &&
                          (kNoiseWords == 0 || prm.err_wt <= 2 * kNoiseWords);

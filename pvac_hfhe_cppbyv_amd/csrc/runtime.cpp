@@ -234,9 +234,6 @@ void flush_timers(pvac_hip_ctx* c) {
     }
 }
 
-#ifndef PVAC_FAST_READBACK   // A/B builds only: pinned read-back words and a spinning wait for them
-#define PVAC_FAST_READBACK 1
-#endif
 // The short host waits of a plan (its totals) and of exec (the redo count): a blocking
 // hipStreamSynchronize wakes tens of microseconds after the copy lands, so spin on hipStreamQuery
 // (up to spin_us, then block) and read into pinned words (a pageable destination stages the copy).
@@ -244,7 +241,6 @@ void flush_timers(pvac_hip_ctx* c) {
 // (several threads per device) spin 200 us and then block, so they do not hold cores and the HIP
 // runtime's locks while their kernels run.
 hipError_t read_back(pvac_hip_ctx* c, void* dst, const void* src, size_t bytes) {
-#if PVAC_FAST_READBACK
     if (c->pin && bytes <= 256) {
         hipError_t e = hipMemcpyAsync(c->pin, src, bytes, hipMemcpyDeviceToHost, c->stream);
         if (e != hipSuccess) return e;
@@ -260,7 +256,6 @@ hipError_t read_back(pvac_hip_ctx* c, void* dst, const void* src, size_t bytes) 
         if (e == hipSuccess) std::memcpy(dst, c->pin, bytes);
         return e;
     }
-#endif
     hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     return e;
@@ -332,26 +327,6 @@ uint32_t ceil_log2(uint64_t x) {
     return b;
 }
 
-// Per-A-edge emit order for eligible pairs (large_desc::iblk). A/B builds only (make variant-f, never
-// the shipped library): -DPVAC_LARGE_IBLK=0 keeps the n/16 block marks for every pair, and so does
-// -DPVAC_LARGE_PRODUCTS_COL26, whose per-task products kernel does not see an A layer's keys in one
-// workgroup.
-#ifndef PVAC_LARGE_IBLK
-#define PVAC_LARGE_IBLK 1
-#endif
-constexpr bool large_iblk_enabled() {
-#ifdef PVAC_LARGE_PRODUCTS_COL26
-    return false;
-#else
-    return PVAC_LARGE_IBLK != 0;
-#endif
-}
-// Direct mode for iblk pairs (large_desc::direct): A/B builds with -DPVAC_LARGE_DIRECT=0 keep every
-// iblk pair on the per-key-sums layout
-#ifndef PVAC_LARGE_DIRECT
-#define PVAC_LARGE_DIRECT 1
-#endif
-
 // Scratch layout of one general-path pair (k_mul_large.hip), offsets relative to 0; the
 // executor rebases them into the arena. 64-bit arrays on even words, 16-byte arrays on
 // multiples of four.
@@ -383,10 +358,10 @@ int build_large_desc(large_desc& d, uint64_t pair, uint64_t LA, uint64_t LB, uin
     d.hbits = std::max<uint32_t>(1, ceil_log2(2 * std::max<uint64_t>(keys, 1)));
     d.g_head = d.g_next = kNoGrp;
     // per-A-edge emit order (k_mul_large.hip): static groups and the A-layer-major products kernel
-    d.iblk = static_grp && LB <= kLaMaxLB && nA >= 1 && nB >= 1 && nB <= kIblkMaxNB && large_iblk_enabled() ? 1u : 0u;
+    d.iblk = static_grp && LB <= kLaMaxLB && nA >= 1 && nB >= 1 && nB <= kIblkMaxNB ? 1u : 0u;
     // (direct A ids and writer lists pack an A edge with its dense cell: A edges < 2^21, 2 B <= 2^11)
     // (and k_large_products_direct's LDS: the digit table, LB staged B layers and their sums)
-    d.direct = d.iblk && allow_direct && PVAC_LARGE_DIRECT && nA < (1ull << 21) && Bm <= 1024u &&
+    d.direct = d.iblk && allow_direct && nA < (1ull << 21) && Bm <= 1024u &&
                        large_direct_lds_bytes(Bm, (uint32_t)LB) <= 160u * 1024u
                    ? 1u
                    : 0u;
@@ -502,9 +477,7 @@ int pvac_hip_ctx_create(int device, const pvac_hip_params* prm, pvac_hip_ctx** o
     if (e == hipSuccess) e = hipMalloc(&c->stats, sizeof(plan_stats));
     // the scans' two totals are plan_stats' first words: a plan reads stats and totals back in one copy
     if (e == hipSuccess) c->totals = &c->stats->total_layers;
-#if PVAC_FAST_READBACK
     if (e == hipSuccess) e = hipHostMalloc(&c->pin, 256, hipHostMallocDefault);
-#endif
     if (e != hipSuccess) { pvac_hip_ctx_destroy(c); return PVAC_ENOMEM; }
     *out = c;
     return PVAC_OK;
@@ -884,15 +857,6 @@ int run_large(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_batch* B, c
     if (!rc) rc = ensure_dev(c, c->sel_dev, c->sel_cap, nl, "alloc large descriptor order");
     if (rc) return rc;
     c->sel_host.resize(nl);
-    // A-layers per workgroup and the XCD-aware grid of k_large_products_la: compile-time A/B knobs
-#ifndef PVAC_LA_PER_WG
-#define PVAC_LA_PER_WG kLaPerWG
-#endif
-#ifndef PVAC_LA_XCD
-#define PVAC_LA_XCD 0
-#endif
-    constexpr uint32_t la_per_wg = PVAC_LA_PER_WG, la_xcd = PVAC_LA_XCD;
-    static_assert(la_per_wg >= 1 && la_per_wg <= 64, "A layers per products workgroup");
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 8ull << 30;
     uint64_t budget = std::max<uint64_t>((uint64_t)(free_b / 2) / 4 + c->arena_words, 1ull << 24);
@@ -939,7 +903,7 @@ int run_large(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_batch* B, c
             const uint64_t tasks = (uint64_t)d.LA * d.LB;
             mTa = std::max(mTa, tasks);
             if (d.LB <= kLaMaxLB) {
-                mLa = std::max<uint64_t>(mLa, (d.LA + la_per_wg - 1) / la_per_wg);
+                mLa = std::max<uint64_t>(mLa, (d.LA + kLaPerWG - 1) / kLaPerWG);
             } else {
                 mT = std::max(mT, tasks);
                 c->sel_host[i + q++] = (uint32_t)(k - i);
@@ -1007,8 +971,8 @@ int run_large(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_batch* B, c
         a.A_img = c->img_in;
         a.C_img = c->img_out;
         a.img_count = c->img_out ? c->img_count : nullptr;
-        a.la_per_wg = la_per_wg;
-        a.la_xcd = la_xcd;
+        a.la_per_wg = kLaPerWG;
+        a.la_xcd = 0;
         e = launch_ct_mul_large(a, c->stream);
         if (e != hipSuccess) return hip_fail(c, e, "ct_mul_large");
         c->path_total[1] += j - i;
@@ -1778,11 +1742,6 @@ hipError_t grow_async(T*& p, size_t& cap, size_t need, hipStream_t st) {
     return e;
 }
 
-// intermediate chain steps as dense images (A/B builds: -DPVAC_CHAIN_IMAGE=0 keeps records throughout)
-#ifndef PVAC_CHAIN_IMAGE
-#define PVAC_CHAIN_IMAGE 1
-#endif
-
 struct chain_range {
     uint64_t end = 0;               // last input (exclusive) of this device range
     std::atomic<uint64_t> next{0};  // next chunk's first input
@@ -1948,7 +1907,7 @@ void chain_worker(pvac_hip_ctx* k, chain_shared* sh, chain_range* rg, bool stage
     // intermediate steps hand their C to the next step as dense images (mul_large_args::C_img) unless
     // a caller hook or the gsum check reads every step's records; an image A never meets the fresh
     // kernel, whose pairs have at most kFreshEdgesMax < 2B edges a side
-    const bool use_img = PVAC_CHAIN_IMAGE && !check && !o.after_step && 2u * k->prm.B > kFreshEdgesMax;
+    const bool use_img = !check && !o.after_step && 2u * k->prm.B > kFreshEdgesMax;
     auto hipchk = [&](hipError_t e, const char* where) {
         if (e == hipSuccess) return true;
         sh->failed(e == hipErrorOutOfMemory ? PVAC_ENOMEM : PVAC_EDEVICE,

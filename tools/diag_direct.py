@@ -1,6 +1,6 @@
 """Phase split of k_large_products_direct (GPU box, diagnostic build only): runs the cfg-4 chain on
-one worker stream through lib/exp/libpvac_hip_dirst.so (make variant-f VFILE=k_mul_large VNAME=dirst
-VFLAGS=-DPVAC_DIR_STAMPS) and prints wave 0's s_memtime cycles per phase summed over workgroups:
+one worker stream through lib/libpvac_hip_diag.so (make diag) and prints wave 0's s_memtime cycles
+per phase summed over workgroups:
 0 setup / loop, 1 dense staging (A-layer gather), 2 matrix-core rows, 3 range writer; per A layer;
 the same for k_large_count_la (setup, stage_tt, key records, iblk counts + writer list).
 Usage: python tools/diag_direct.py [inputs]"""
@@ -19,7 +19,7 @@ from pvac_hfhe_cppbyv_amd import Engine, load_library  # noqa: E402
 
 def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
-    lib = load_library(os.path.join(ROOT, "pvac_hfhe_cppbyv_amd", "lib", "exp", "libpvac_hip_dirst.so"))
+    lib = load_library(os.path.join(ROOT, "pvac_hfhe_cppbyv_amd", "lib", "libpvac_hip_diag.so"))
     eng = Engine(device=0, canon_tag=0x5EED0003, lib=lib)
     bench._enc_keys(eng)
     vals = torch.empty(n, dtype=torch.int64, device=eng.device)

@@ -1,5 +1,5 @@
 """A/B timing of k_ct.hip variants (GPU box): bench.py's ct_add / ct_sub / ct_scale leg on the cfg-3
-batch through each library given (make variant-ct); prints the kernel averages.
+batch through each library given (make variant VFILE=k_ct ...); prints the kernel averages.
 Usage: python tools/exp_add.py lib1.so [lib2.so ...]"""
 import json
 import os

@@ -1,6 +1,6 @@
 """Timing experiments on k_ct_mul_fresh (GPU box): cfg-3 batch through each library given, average
-kernel time of the fresh kernel over 5 launches. The experiment libraries (make exp) each remove one
-piece of work, so their outputs are wrong; the point is the marginal cost of that piece.
+kernel time of the fresh kernel over 5 launches (and of the layers kernel), outputs compared with the
+first library's: a variant library (make variant VFILE=k_mul_fresh ...) must be bit-exact.
 Usage: python tools/exp_fresh.py lib1.so [lib2.so ...]"""
 import json
 import os
