@@ -720,37 +720,38 @@ __global__ __launch_bounds__(256) void k_encode_delta(const uint16_t* rows, uint
 // rows_delta for the default geometry (see flip_cols_delta); synchronous; left null when a column
 // does not fit kDeltaBytes (the u16 expansion is used then)
 static hipError_t build_delta_rows(sigma_tables& T, const pvac_hip_params& prm, hipStream_t st) {
-    if (T.rows_delta) { hipFree(T.rows_delta); T.rows_delta = nullptr; }
-    if (!(prm.m_bits == 8192 && prm.x_col_wt == 128 && T.full && T.rows &&
+    T.rows_delta.release();
+    if (!(prm.m_bits == 8192 && prm.x_col_wt == 128 && T.full && T.rows.get() &&
           sigma_wave_words(prm.m_bits, prm.n_bits, prm.x_col_wt) == kFastWaveWords))
         return hipSuccess;
-    uint32_t* ovf = nullptr;
-    hipError_t e = hipMalloc(&T.rows_delta, (size_t)T.n_cols * kDeltaBytes);
-    if (e == hipSuccess) e = hipMalloc(&ovf, 4);
-    if (e == hipSuccess) e = hipMemsetAsync(ovf, 0, 4, st);
+    dev_buf<uint32_t> ovf;
+    const size_t nd = (size_t)T.n_cols * kDeltaBytes;
+    hipError_t e = T.rows_delta.grow(nd, nd);
+    if (e == hipSuccess) e = ovf.grow(1, 1);
+    if (e == hipSuccess) e = hipMemsetAsync(ovf.get(), 0, 4, st);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_encode_delta, dim3((T.n_cols + 255) / 256), dim3(256), 0, st, T.rows, T.rows_delta, T.width,
-                           T.n_cols, ovf);
+        hipLaunchKernelGGL(k_encode_delta, dim3((T.n_cols + 255) / 256), dim3(256), 0, st, T.rows.get(),
+                           T.rows_delta.get(), T.width, T.n_cols, ovf.get());
         e = hipGetLastError();
     }
     uint32_t h = 1;
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, ovf, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, ovf.get(), 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    hipFree(ovf);
-    if (e != hipSuccess || h) { hipFree(T.rows_delta); T.rows_delta = nullptr; }
+    if (e != hipSuccess || h) T.rows_delta.release();
     return e;
 }
 
 // rows_fast for the default geometry (see flip_cols_fast); other geometries keep rows only
 static hipError_t build_fast_rows(sigma_tables& T, const pvac_hip_params& prm, hipStream_t st) {
-    if (T.rows_fast) { hipFree(T.rows_fast); T.rows_fast = nullptr; }
+    T.rows_fast.release();
     if (!(prm.m_bits == 8192 && prm.x_col_wt == 128 && T.full && T.width % 8 == 0 && T.width >= 8 &&
           sigma_wave_words(prm.m_bits, prm.n_bits, prm.x_col_wt) == kFastWaveWords))
         return hipSuccess;
-    hipError_t e = hipMalloc(&T.rows_fast, (size_t)T.n_cols * T.width * 2);
-    if (e != hipSuccess) { T.rows_fast = nullptr; return e; }
-    hipLaunchKernelGGL(k_encode_fast, dim3((T.n_cols + 255) / 256), dim3(256), 0, st, T.rows, T.rows_fast, T.width,
-                       T.n_cols);
+    const size_t nr = (size_t)T.n_cols * T.width;
+    const hipError_t e = T.rows_fast.grow(nr, nr);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_encode_fast, dim3((T.n_cols + 255) / 256), dim3(256), 0, st, T.rows.get(), T.rows_fast.get(),
+                       T.width, T.n_cols);
     return hipGetLastError();
 }
 
@@ -779,35 +780,24 @@ void sha256_host(const uint8_t* p, size_t n, uint8_t out[32]) {
     }
 }
 
-
-void sigma_tables_free(sigma_tables& T) {
-    hipFree(T.rows);
-    hipFree(T.counts);
-    hipFree(T.rows_fast);
-    hipFree(T.rows_delta);
-    T = sigma_tables{};
-}
-
 // A copy of src's device tables for a context on dst_dev (same or another device: peer copies
 // over xGMI); synchronous on st, which must belong to dst_dev.
 hipError_t sigma_tables_clone(sigma_tables& dst, const sigma_tables& src, int dst_dev, int src_dev, hipStream_t st) {
-    sigma_tables_free(dst);
+    dst = sigma_tables{};
     if (!src.ready) return hipSuccess;
-    const size_t nr = (size_t)src.n_cols * src.width * 2, nc = (size_t)src.n_cols * 4,
-                 nd = (size_t)src.n_cols * kDeltaBytes;
-    auto one = [&](void** d, const void* s, size_t bytes) -> hipError_t {
-        if (!s) return hipSuccess;
-        hipError_t e = hipMalloc(d, bytes);
-        if (e == hipSuccess) e = hipMemcpyPeerAsync(*d, dst_dev, s, src_dev, bytes, st);
+    auto one = [&](auto& d, const auto& s) -> hipError_t {   // every table is allocated at its exact size
+        if (!s.get()) return hipSuccess;
+        hipError_t e = d.grow(s.capacity(), s.capacity());
+        if (e == hipSuccess) e = hipMemcpyPeerAsync(d.get(), dst_dev, s.get(), src_dev, s.capacity() * sizeof(*s.get()), st);
         return e;
     };
-    hipError_t e = one((void**)&dst.rows, src.rows, nr);
-    if (e == hipSuccess) e = one((void**)&dst.counts, src.counts, nc);
-    if (e == hipSuccess) e = one((void**)&dst.rows_fast, src.rows_fast, nr);
-    if (e == hipSuccess) e = one((void**)&dst.rows_delta, src.rows_delta, nd);
+    hipError_t e = one(dst.rows, src.rows);
+    if (e == hipSuccess) e = one(dst.counts, src.counts);
+    if (e == hipSuccess) e = one(dst.rows_fast, src.rows_fast);
+    if (e == hipSuccess) e = one(dst.rows_delta, src.rows_delta);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
-        sigma_tables_free(dst);
+        dst = sigma_tables{};
         return e;
     }
     dst.width = src.width;
@@ -818,10 +808,10 @@ hipError_t sigma_tables_clone(sigma_tables& dst, const sigma_tables& src, int ds
 }
 
 static hipError_t alloc_tables(sigma_tables& T, uint32_t n_cols, uint32_t width) {
-    sigma_tables_free(T);
-    hipError_t e = hipMalloc(&T.rows, (size_t)n_cols * width * 2);
-    if (e == hipSuccess) e = hipMalloc(&T.counts, (size_t)n_cols * 4);
-    if (e != hipSuccess) { sigma_tables_free(T); return e; }
+    T = sigma_tables{};
+    hipError_t e = T.rows.grow((size_t)n_cols * width, (size_t)n_cols * width);
+    if (e == hipSuccess) e = T.counts.grow(n_cols, n_cols);
+    if (e != hipSuccess) { T = sigma_tables{}; return e; }
     T.width = width;
     T.n_cols = n_cols;
     return hipSuccess;
@@ -853,8 +843,8 @@ hipError_t sigma_tables_from_dense(sigma_tables& T, const pvac_hip_params& prm, 
     }
     hipError_t e = alloc_tables(T, prm.n_bits, width);
     T.full = std::all_of(cnt.begin(), cnt.end(), [&](uint32_t k) { return k == width; });
-    if (e == hipSuccess) e = hipMemcpyAsync(T.rows, rows.data(), rows.size() * 2, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(T.counts, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(T.rows.get(), rows.data(), rows.size() * 2, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(T.counts.get(), cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = build_fast_rows(T, prm, st);
     if (e == hipSuccess) e = build_delta_rows(T, prm, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -870,7 +860,7 @@ hipError_t sigma_tables_generate(sigma_tables& T, const pvac_hip_params& prm, ui
     if (e != hipSuccess) return e;
     T.full = T.width == prm.h_col_wt;   // gen_H draws exactly h_col_wt distinct rows per column
     const size_t lds = (size_t)4 * (prm.m_bits / 32) * 4;
-    hipLaunchKernelGGL(k_gen_H, dim3(2048), dim3(256), lds, st, T.rows, T.counts, T.width, prm.m_bits, prm.n_bits,
+    hipLaunchKernelGGL(k_gen_H, dim3(2048), dim3(256), lds, st, T.rows.get(), T.counts.get(), T.width, prm.m_bits, prm.n_bits,
                        prm.h_col_wt, prm.canon_tag);
     e = hipGetLastError();
     if (e == hipSuccess) e = build_fast_rows(T, prm, st);
@@ -878,7 +868,7 @@ hipError_t sigma_tables_generate(sigma_tables& T, const pvac_hip_params& prm, ui
     if (e != hipSuccess) return e;
     if (digest) {
         std::vector<uint16_t> rows((size_t)prm.n_bits * T.width);
-        e = hipMemcpyAsync(rows.data(), T.rows, rows.size() * 2, hipMemcpyDeviceToHost, st);
+        e = hipMemcpyAsync(rows.data(), T.rows.get(), rows.size() * 2, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) return e;
         // H_digest = SHA-256("H|v2" || le64 m || le64 n || le64 wt || column bytes) (matrix.hpp:218-250)
@@ -912,7 +902,7 @@ hipError_t launch_sigma(const sigma_tables& T, const pvac_hip_params& prm, const
     a.X = X;
     a.salts = salts;
     a.salt_pos = salt_pos;
-    a.rows = T.rows;
+    a.rows = T.rows.get();
     // Column expansion: byte-delta tables (default), else u16 rows with per-wave images, else the
     // per-lane-group image copies, else the generic guarded loop. PVAC_SIGMA_PATH = delta | u16 |
     // copies | generic caps the choice (read per launch: A/B runs and the tests of every path).
@@ -924,9 +914,9 @@ hipError_t launch_sigma(const sigma_tables& T, const pvac_hip_params& prm, const
     const bool fast_ok = prm.m_bits == 8192 && prm.x_col_wt == 128 && T.full &&
                          sigma_wave_words(prm.m_bits, prm.n_bits, prm.x_col_wt) == kFastWaveWords &&
                          (kNoiseWords == 0 || prm.err_wt <= 2 * kNoiseWords);
-    a.rows_fast = (fast_ok && path <= 1) ? T.rows_fast : nullptr;
-    a.rows_delta = (a.rows_fast && path == 0) ? T.rows_delta : nullptr;
-    a.counts = T.counts;
+    a.rows_fast = (fast_ok && path <= 1) ? T.rows_fast.get() : nullptr;
+    a.rows_delta = (a.rows_fast && path == 0) ? T.rows_delta.get() : nullptr;
+    a.counts = T.counts.get();
     a.width = T.width;
     a.full = (T.full && path <= 2) ? 1u : 0u;
     a.canon = prm.canon_tag;

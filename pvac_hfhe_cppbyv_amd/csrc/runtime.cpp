@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "dev_mem.hpp"
 #include "sigma.hpp"
 #include "sha256.hpp"
 
@@ -38,21 +39,16 @@ struct timer_rec {
 
 // one output batch of a chain worker (pvac_hip_ct_mul_chain): stream-ordered allocations that grow
 struct chain_set {
-    uint64_t* l_off = nullptr;
-    uint64_t* l_cnt = nullptr;
-    uint64_t* e_off = nullptr;
-    uint64_t* e_cnt = nullptr;
-    size_t n_cap = 0;
-    pvac_layer* layers = nullptr;
-    size_t l_cap = 0;
-    uint64_t* meta = nullptr;
-    uint64_t* w_lo = nullptr;
-    uint64_t* w_hi = nullptr;
-    size_t e_cap = 0;
-    uint64_t* sigma = nullptr;   // final step with PVAC_MUL_WITH_SIGMA: 1 KiB per edge slot
-    size_t s_cap = 0;            // edge slots of sigma
-    uint32_t* img = nullptr;     // per pair: 1 = this step's C is a dense image (mul_large_args::C_img)
-    size_t img_cap = 0;
+    dev_stream_buf<uint64_t> l_off, l_cnt, e_off, e_cnt;
+    dev_stream_buf<pvac_layer> layers;
+    dev_stream_buf<uint64_t> meta, w_lo, w_hi;
+    dev_stream_buf<uint64_t> sigma;   // final step with PVAC_MUL_WITH_SIGMA: 1 KiB per edge slot
+    dev_stream_buf<uint32_t> img;     // per pair: 1 = this step's C is a dense image (mul_large_args::C_img)
+    void release(hipStream_t st) {
+        for (dev_stream_buf<uint64_t>* b : {&l_off, &l_cnt, &e_off, &e_cnt, &meta, &w_lo, &w_hi, &sigma}) b->release(st);
+        layers.release(st);
+        img.release(st);
+    }
 };
 
 }  // namespace
@@ -65,40 +61,33 @@ struct pvac_hip_ctx {
     pvac_hip_params prm{};
     std::string err;
     // device tables / scratch
-    uint32_t* nb_table = nullptr;
-    uint64_t* nb_magic = nullptr;
-    uint8_t* pair_class = nullptr;
-    uint32_t* pair_status = nullptr;
-    fresh_rec* fresh_recs = nullptr;   // per-pair header records of the fresh ct_mul path
+    dev_buf<uint32_t> nb_table;
+    dev_buf<uint64_t> nb_magic;
+    // the pair scratch, grown together by ensure_pairs (8 words of large_info per pair)
+    dev_buf<uint8_t> pair_class;
+    dev_buf<uint32_t> pair_status;
+    dev_buf<fresh_rec> fresh_recs;   // per-pair header records of the fresh ct_mul path
+    dev_buf<uint64_t> large_ids, large_info;
+    dev_buf<uint64_t> redo_ids;      // fresh-kernel pairs left to the general path (a key sum of 0)
+    dev_buf<unsigned int> redo_cnt;
     std::vector<merge_pair_info> merge_host;   // over-budget ct_add pairs of the latest add plan
-    void* merge_scratch = nullptr;
-    size_t merge_cap = 0;
-    unsigned long long* merge_counters = nullptr;
-    uint64_t* powg = nullptr;          // pk.powg_B on the device, B x (lo, hi)
+    dev_buf<uint8_t> merge_scratch;
+    dev_buf<unsigned long long> merge_counters;
+    dev_buf<uint64_t> powg;            // pk.powg_B on the device, B x (lo, hi)
     uint32_t powg_n = 0;
-    void* dec_scratch = nullptr;
-    size_t dec_cap = 0;
-    uint64_t* dec_roff = nullptr;
-    size_t dec_roff_cap = 0;
+    dev_buf<uint8_t> dec_scratch;
+    dev_buf<uint64_t> dec_roff;
     // LPN PRF key material (SecKey) and pk.H_digest
     uint64_t prf_k[4] = {0, 0, 0, 0};
-    uint64_t* lpn_s = nullptr;
+    dev_buf<uint64_t> lpn_s;
     uint32_t lpn_words = 0, lpn_t = 0, tau_num = 0, tau_den = 0;
     bool have_secret = false;
     uint8_t H_digest[32] = {0};
     bool have_digest = false;
     bool aes_tables = false;
-    uint8_t* prf_req = nullptr;
-    size_t prf_req_cap = 0;
-    uint64_t* prf_core = nullptr;
-    size_t prf_core_cap = 0;
-    uint8_t* enc_arena = nullptr;
-    size_t enc_arena_cap = 0;
-    uint64_t* large_ids = nullptr;
-    uint64_t* large_info = nullptr;
-    uint64_t* redo_ids = nullptr;        // fresh-kernel pairs left to the general path (a key sum of 0)
-    unsigned int* redo_cnt = nullptr;
-    size_t pair_cap = 0;
+    dev_buf<uint8_t> prf_req;
+    dev_buf<uint64_t> prf_core;
+    dev_buf<uint8_t> enc_arena;
     // general ct_mul path: host descriptors of the last plan, device copies, scratch arena
     std::vector<large_desc> large_host;
     std::vector<large_desc> large_exec;
@@ -107,32 +96,23 @@ struct pvac_hip_ctx {
     uint64_t redo_total = 0;           // pairs re-run by redo_fresh_pairs since the context was created
     uint64_t path_total[4] = {};       // pair launches: fresh kernel, general path, its iblk order, direct mode
     double noise_bits = 120.0, noise_t2 = 0.55, noise_slope = 16.0;   // Params noise fields (enc plan_noise)
-    large_desc* desc_dev = nullptr;
-    size_t desc_cap = 0;
-    uint32_t* sel_dev = nullptr;       // products: descriptor order per sub-batch (A-layer-major class first)
-    size_t sel_cap = 0;
+    dev_buf<large_desc> desc_dev;
+    dev_buf<uint32_t> sel_dev;         // products: descriptor order per sub-batch (A-layer-major class first)
     std::vector<uint32_t> sel_host;
-    uint32_t* arena = nullptr;
-    size_t arena_words = 0;
+    dev_buf<uint32_t> arena;           // in 32-bit words
     // static bucket-group tables of the last plan (one per distinct bucket count) + build scratch
-    uint32_t* grp = nullptr;
-    size_t grp_cap = 0;
-    uint32_t* grp_tmp = nullptr;
-    size_t grp_tmp_cap = 0;
-    uint32_t* salt_pos = nullptr;
-    size_t salt_cap = 0;
-    mul_fresh_args* fresh_args = nullptr;   // device copy of the fresh kernel's arguments
+    dev_buf<uint32_t> grp, grp_tmp;
+    dev_buf<uint32_t> salt_pos;
+    dev_buf<mul_fresh_args> fresh_args;     // device copy of the fresh kernel's arguments
     mul_fresh_args fresh_args_host{};
     bool fresh_args_uploaded = false;       // the device copy holds fresh_args_host
     bool redo_cnt_dirty = true;             // redo_cnt may be nonzero (zeroed before the next exec)
-    uint64_t* scan_scratch = nullptr;
-    size_t scan_cap = 0;
-    plan_stats* stats = nullptr;
-    unsigned int* check_buf = nullptr;   // gsum check: 4 layer maxima, then a u64 failure count
-    uint8_t* check_scratch = nullptr;    // gsum check: layer tables beyond LDS (global slabs)
-    size_t check_scratch_cap = 0;
-    unsigned long long* totals = nullptr;   // [2]: &stats->total_layers (layer and edge slot totals)
-    void* pin = nullptr;                    // pinned host words for the plan's and exec's read-backs
+    dev_buf<uint64_t> scan_scratch;
+    dev_buf<plan_stats> stats;
+    dev_buf<unsigned int> check_buf;     // gsum check: 4 layer maxima, then a u64 failure count
+    dev_buf<uint8_t> check_scratch;      // gsum check: layer tables beyond LDS (global slabs)
+    unsigned long long* totals = nullptr;   // [2]: &stats->total_layers (layer and edge slot totals), not owned
+    void* pin = nullptr;   // pinned host words for the plan's and exec's read-backs (hipHostFree in ctx_destroy)
     sigma_tables H;
     // timing
     bool timing = false;
@@ -146,10 +126,8 @@ struct pvac_hip_ctx {
     uint32_t* img_in = nullptr;
     uint32_t* img_out = nullptr;
     unsigned long long* img_count = nullptr;   // chain: pair-steps written as images (chain_stats' last word)
-    uint64_t* img_tmp = nullptr;       // image -> records: 3 words per edge of the pairs converted
-    size_t img_tmp_cap = 0;
-    uint64_t* img_pairs = nullptr;     // [2 n]: pair ids, then their offsets in img_tmp
-    size_t img_pairs_cap = 0;
+    dev_buf<uint64_t> img_tmp;         // image -> records: 3 words per edge of the pairs converted
+    dev_buf<uint64_t> img_pairs;       // [2 n]: pair ids, then their offsets in img_tmp
     uint32_t img_grid_y = 65535;       // pairs per image -> records launch (PVAC_CHAIN_IMG_BATCH2: 2)
     uint32_t spin_us = 50000;          // read_back's spin before a blocking wait (chain workers: 200)
     // pvac_hip_ct_mul_chain: worker contexts (own stream / arena), and a worker's own buffers
@@ -157,13 +135,10 @@ struct pvac_hip_ctx {
     chain_set chain_bufs[2];
     chain_set chain_stage;                   // a worker's staged chunk inputs (another device, or STAGE)
     chain_set chain_stage_op;                // ... and its staged per-step operand (pvac_chain_opts::operands)
-    uint64_t* chain_nonces = nullptr;
-    size_t chain_nonce_cap = 0;
-    uint64_t* chain_salts = nullptr;         // final-step salts (WITH_SIGMA)
-    size_t chain_salt_cap = 0;
-    uint64_t* chain_out = nullptr;           // digests / counts of a chunk before the copy to X's device
-    size_t chain_out_cap = 0;
-    unsigned long long* chain_stats = nullptr;   // [2 * PVAC_CHAIN_MAX_DEPTH + 1]: edges / products, image pair-steps
+    dev_stream_buf<uint64_t> chain_nonces;
+    dev_stream_buf<uint64_t> chain_salts;    // final-step salts (WITH_SIGMA)
+    dev_stream_buf<uint64_t> chain_out;      // digests / counts of a chunk before the copy to X's device
+    dev_buf<unsigned long long> chain_stats;     // [2 * PVAC_CHAIN_MAX_DEPTH + 1]: edges / products, image pair-steps
     std::vector<int64_t> chain_layout;          // the last call's (streams, chunk, n_devices, ordinals...)
     uint64_t H_gen = 0;                      // bumped whenever H is set (a worker's copy follows it)
     uint64_t H_from = 0;                     // worker: the parent's H_gen its H copy was taken from
@@ -261,64 +236,37 @@ hipError_t read_back(pvac_hip_ctx* c, void* dst, const void* src, size_t bytes) 
     return e;
 }
 
-int ensure_scan(pvac_hip_ctx* c, size_t n);
-
-int ensure_pairs(pvac_hip_ctx* c, size_t n) {
-    if (n > c->pair_cap) {
-        hipFree(c->pair_class);
-        hipFree(c->pair_status);
-        hipFree(c->large_ids);
-        hipFree(c->large_info);
-        hipFree(c->redo_ids);
-        hipFree(c->fresh_recs);
-        c->fresh_recs = nullptr;
-        c->redo_ids = nullptr;
-        c->pair_class = nullptr;
-        c->pair_status = nullptr;
-        c->large_ids = nullptr;
-        c->large_info = nullptr;
-        size_t cap = std::max<size_t>(n, 1024);
-        hipError_t e = hipMalloc(&c->pair_class, cap);
-        if (e == hipSuccess) e = hipMalloc(&c->pair_status, cap * 4);
-        if (e == hipSuccess) e = hipMalloc(&c->large_ids, cap * 8);
-        if (e == hipSuccess) e = hipMalloc(&c->large_info, cap * 64);   // 5 (mul) or 8 (add merge) words per pair
-        if (e == hipSuccess) e = hipMalloc(&c->fresh_recs, cap * sizeof(fresh_rec));
-        if (e == hipSuccess) e = hipMalloc(&c->redo_ids, cap * 8);
-        if (e == hipSuccess && !c->redo_cnt) e = hipMalloc(&c->redo_cnt, 16);
-        if (e != hipSuccess) { c->pair_cap = 0; return hip_fail(c, e, "alloc pair scratch"); }
-        c->pair_cap = cap;
-    }
-    return ensure_scan(c, n);
-}
-
 // the exclusive scans' scratch for n counts
 int ensure_scan(pvac_hip_ctx* c, size_t n) {
     const size_t sw = scan_scratch_words(n);
-    if (sw > c->scan_cap) {
-        hipFree(c->scan_scratch);
-        c->scan_scratch = nullptr;
-        hipError_t e = hipMalloc(&c->scan_scratch, sw * 8);
-        if (e != hipSuccess) { c->scan_cap = 0; return hip_fail(c, e, "alloc scan scratch"); }
-        c->scan_cap = sw;
+    return hip_fail(c, c->scan_scratch.grow(sw, sw), "alloc scan scratch");
+}
+
+// the six per-pair arrays are grown together (redo_ids last: its capacity stands for all of them)
+int ensure_pairs(pvac_hip_ctx* c, size_t n) {
+    hipError_t e = hipSuccess;
+    if (n > c->redo_ids.capacity()) {
+        c->pair_class.release();
+        c->pair_status.release();
+        c->large_ids.release();
+        c->large_info.release();
+        c->redo_ids.release();
+        c->fresh_recs.release();
+        const size_t cap = std::max<size_t>(n, 1024);
+        e = c->pair_class.grow(n, cap);
+        if (e == hipSuccess) e = c->pair_status.grow(n, cap);
+        if (e == hipSuccess) e = c->large_ids.grow(n, cap);
+        if (e == hipSuccess) e = c->large_info.grow(8 * n, 8 * cap);   // 5 (mul) or 8 (add merge) words per pair
+        if (e == hipSuccess) e = c->fresh_recs.grow(n, cap);
+        if (e == hipSuccess) e = c->redo_ids.grow(n, cap);
     }
-    return PVAC_OK;
+    if (e == hipSuccess) e = c->redo_cnt.grow(4, 4);
+    if (e != hipSuccess) return hip_fail(c, e, "alloc pair scratch");
+    return ensure_scan(c, n);
 }
 
 bool batch_ok(const pvac_ct_batch* X) {
     return X && (X->n == 0 || (X->l_off && X->l_cnt && X->e_off && X->e_cnt));
-}
-
-template <typename T>
-int ensure_dev(pvac_hip_ctx* c, T*& p, size_t& cap, size_t n, const char* what) {
-    if (n <= cap) return PVAC_OK;
-    hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = std::max<size_t>(n, 1024);
-    hipError_t e = hipMalloc(&p, want * sizeof(T));
-    if (e != hipSuccess) return hip_fail(c, e, what);
-    cap = want;
-    return PVAC_OK;
 }
 
 uint32_t ceil_log2(uint64_t x) {
@@ -456,115 +404,69 @@ int pvac_hip_ctx_create(int device, const pvac_hip_params* prm, pvac_hip_ctx** o
     c->device = device;
     c->prm = *prm;
     hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) { delete c; return PVAC_EDEVICE; }
+    if (e != hipSuccess) { pvac_hip_ctx_destroy(c); return PVAC_EDEVICE; }
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
         c->num_cus = cus;
     e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete c; return PVAC_EDEVICE; }
+    if (e != hipSuccess) { pvac_hip_ctx_destroy(c); return PVAC_EDEVICE; }
     c->own_stream = true;
     std::vector<uint32_t> nb(kNbTableLen);
     std::vector<uint64_t> mg(kNbTableLen);
     for (uint32_t n = 0; n < kNbTableLen; ++n) {
         nb[n] = (uint32_t)bucket_count_after_reserve(n);
         mg[n] = make_fastmod64(nb[n]).m;
-        if (nb[n] == 0 || nb[n] > 0xFFFFu) { delete c; return PVAC_ERANGE; }   // fresh_rec.nbk is u16
+        if (nb[n] == 0 || nb[n] > 0xFFFFu) { pvac_hip_ctx_destroy(c); return PVAC_ERANGE; }   // fresh_rec.nbk is u16
     }
-    e = hipMalloc(&c->nb_table, nb.size() * 4);
-    if (e == hipSuccess) e = hipMemcpy(c->nb_table, nb.data(), nb.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&c->nb_magic, mg.size() * 8);
-    if (e == hipSuccess) e = hipMemcpy(c->nb_magic, mg.data(), mg.size() * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&c->stats, sizeof(plan_stats));
+    e = c->nb_table.grow(nb.size(), nb.size());
+    if (e == hipSuccess) e = hipMemcpy(c->nb_table.get(), nb.data(), nb.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = c->nb_magic.grow(mg.size(), mg.size());
+    if (e == hipSuccess) e = hipMemcpy(c->nb_magic.get(), mg.data(), mg.size() * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = c->stats.grow(1, 1);
     // the scans' two totals are plan_stats' first words: a plan reads stats and totals back in one copy
-    if (e == hipSuccess) c->totals = &c->stats->total_layers;
+    if (e == hipSuccess) c->totals = &c->stats.get()->total_layers;
     if (e == hipSuccess) e = hipHostMalloc(&c->pin, 256, hipHostMallocDefault);
     if (e != hipSuccess) { pvac_hip_ctx_destroy(c); return PVAC_ENOMEM; }
     *out = c;
     return PVAC_OK;
 }
 
-// a chain worker's output batches (stream-ordered frees on its stream; the caller synchronises)
-static void free_chain_sets(pvac_hip_ctx* c) {
-    for (chain_set* b : {&c->chain_bufs[0], &c->chain_bufs[1], &c->chain_stage, &c->chain_stage_op}) {
-        for (void* q : {(void*)b->l_off, (void*)b->l_cnt, (void*)b->e_off, (void*)b->e_cnt, (void*)b->layers,
-                        (void*)b->meta, (void*)b->w_lo, (void*)b->w_hi, (void*)b->sigma, (void*)b->img})
-            if (q) hipFreeAsync(q, c->stream);
-        *b = chain_set{};
-    }
+// a context's stream-ordered buffers (a chain worker's output batches, nonce / salt / result words)
+// go back on its stream; the caller synchronises
+static void release_stream_ordered(pvac_hip_ctx* c) {
+    for (chain_set* b : {&c->chain_bufs[0], &c->chain_bufs[1], &c->chain_stage, &c->chain_stage_op}) b->release(c->stream);
+    c->chain_nonces.release(c->stream);
+    c->chain_salts.release(c->stream);
+    c->chain_out.release(c->stream);
 }
 
-// everything a chain worker grew during a call (output batches, nonce / salt / result words, image
-// scratch, the general-path arena); the caller selected the worker's device
+// everything a chain worker grew during a call (the above, image scratch, the general-path arena,
+// the gsum check's slabs); the caller selected the worker's device
 static hipError_t release_chain_worker(pvac_hip_ctx* k) {
-    free_chain_sets(k);
-    for (void** q : {(void**)&k->chain_nonces, (void**)&k->chain_salts, (void**)&k->chain_out}) {
-        if (*q) hipFreeAsync(*q, k->stream);
-        *q = nullptr;
-    }
-    k->chain_nonce_cap = k->chain_salt_cap = k->chain_out_cap = 0;
+    release_stream_ordered(k);
     const hipError_t e = hipStreamSynchronize(k->stream);
-    for (void** q : {(void**)&k->img_tmp, (void**)&k->img_pairs, (void**)&k->arena, (void**)&k->check_scratch}) {
-        hipFree(*q);
-        *q = nullptr;
-    }
-    k->img_tmp_cap = k->img_pairs_cap = k->check_scratch_cap = 0;
-    k->arena_words = 0;
+    k->img_tmp.release();
+    k->img_pairs.release();
+    k->arena.release();
+    k->check_scratch.release();
     return e;
 }
 
+// The only deleter of a context (ctx_create's failure exits included): workers first, then this
+// context's device, its stream drained, timer events, the stream-ordered buffers while the stream
+// lives, the stream itself; the members' destructors free the rest before the caller's device returns.
 int pvac_hip_ctx_destroy(pvac_hip_ctx* c) {
     if (!c) return PVAC_OK;
-    int caller_dev = -1;   // the calling thread's device, restored on return
-    if (hipGetDevice(&caller_dev) != hipSuccess) caller_dev = -1;
-    hipSetDevice(c->device);
     for (pvac_hip_ctx* k : c->chain_kids) pvac_hip_ctx_destroy(k);
-    c->chain_kids.clear();
-    hipSetDevice(c->device);   // each worker's destroy selected the worker's device
+    device_guard dev(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
     flush_timers(c);
     for (hipEvent_t e : c->ev_pool) hipEventDestroy(e);
-    c->ev_pool.clear();
-    free_chain_sets(c);
-    for (void* q : {(void*)c->chain_nonces, (void*)c->chain_salts, (void*)c->chain_out})
-        if (q) hipFreeAsync(q, c->stream);
+    release_stream_ordered(c);
     if (c->stream) hipStreamSynchronize(c->stream);
-    hipFree(c->chain_stats);
-    hipFree(c->nb_table);
-    hipFree(c->nb_magic);
-    hipFree(c->pair_class);
-    hipFree(c->pair_status);
-    hipFree(c->fresh_recs);
-    hipFree(c->large_ids);
-    hipFree(c->large_info);
-    hipFree(c->redo_ids);
-    hipFree(c->redo_cnt);
-    hipFree(c->img_tmp);
-    hipFree(c->img_pairs);
-    hipFree(c->desc_dev);
-    hipFree(c->sel_dev);
-    hipFree(c->arena);
-    hipFree(c->grp);
-    hipFree(c->grp_tmp);
-    hipFree(c->salt_pos);
-    hipFree(c->fresh_args);
-    hipFree(c->merge_scratch);
-    hipFree(c->merge_counters);
-    hipFree(c->powg);
-    hipFree(c->lpn_s);
-    hipFree(c->prf_req);
-    hipFree(c->prf_core);
-    hipFree(c->enc_arena);
-    hipFree(c->dec_scratch);
-    hipFree(c->dec_roff);
-    hipFree(c->scan_scratch);
-    hipFree(c->stats);
-    if (c->pin) hipHostFree(c->pin);
-    hipFree(c->check_buf);
-    hipFree(c->check_scratch);
-    sigma_tables_free(c->H);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
+    if (c->pin) hipHostFree(c->pin);
     delete c;
-    if (caller_dev >= 0) hipSetDevice(caller_dev);
     return PVAC_OK;
 }
 
@@ -616,7 +518,7 @@ int pvac_hip_ct_mul_status(pvac_hip_ctx* c, uint32_t* out, size_t n) {
     if (!c || (!out && n)) return fail(c, PVAC_EINVAL, "ct_mul_status: bad arguments");
     if (!n) return PVAC_OK;
     if (n > c->last_mul_pairs) return fail(c, PVAC_EINVAL, "ct_mul_status: more pairs than the last ct_mul_exec held");
-    const hipError_t e = hipMemcpyAsync(out, c->pair_status, n * 4, hipMemcpyDeviceToDevice, c->stream);
+    const hipError_t e = hipMemcpyAsync(out, c->pair_status.get(), n * 4, hipMemcpyDeviceToDevice, c->stream);
     return e == hipSuccess ? PVAC_OK : hip_fail(c, e, "ct_mul_status");
 }
 
@@ -716,8 +618,8 @@ int plan_static_groups(pvac_hip_ctx* c) {
         tmp_max = std::max<uint64_t>(tmp_max, 1ull << std::max<uint32_t>(1, ceil_log2(2 * kv.second)));
     }
     if (cfg.empty() || cfg.size() > kMaxCfg || words > kMaxWords) return PVAC_OK;   // dynamic chains
-    int rc = ensure_dev(c, c->grp, c->grp_cap, words, "alloc bucket-group tables");
-    if (!rc) rc = ensure_dev(c, c->grp_tmp, c->grp_tmp_cap, 3 * tmp_max, "alloc bucket-group scratch");
+    int rc = hip_fail(c, c->grp.grow_floor(words), "alloc bucket-group tables");
+    if (!rc) rc = hip_fail(c, c->grp_tmp.grow_floor(3 * tmp_max), "alloc bucket-group scratch");
     if (rc) return rc;
     std::map<uint64_t, uint64_t> off;   // bucket count -> head offset (next = head + S_max)
     uint64_t o = 0;
@@ -725,11 +627,11 @@ int plan_static_groups(pvac_hip_ctx* c) {
         const uint64_t Sm = kv.second;
         const uint32_t hb = std::max<uint32_t>(1, ceil_log2(2 * Sm));
         const uint64_t hcap = 1ull << hb;
-        unsigned long long* tk = (unsigned long long*)c->grp_tmp;   // [hcap] u64 keys, then [hcap] u32 heads
-        uint32_t* th = c->grp_tmp + 2 * hcap;
-        hipError_t e = hipMemsetAsync(c->grp_tmp, 0, 3 * hcap * 4, c->stream);
+        unsigned long long* tk = (unsigned long long*)c->grp_tmp.get();   // [hcap] u64 keys, then [hcap] u32 heads
+        uint32_t* th = c->grp_tmp.get() + 2 * hcap;
+        hipError_t e = hipMemsetAsync(c->grp_tmp.get(), 0, 3 * hcap * 4, c->stream);
         if (e == hipSuccess)
-            e = launch_grp_build(make_fastmod64(kv.first), c->prm.B, Sm, hb, c->grp + o, c->grp + o + Sm, tk, th,
+            e = launch_grp_build(make_fastmod64(kv.first), c->prm.B, Sm, hb, c->grp.get() + o, c->grp.get() + o + Sm, tk, th,
                                  c->stream);
         if (e != hipSuccess) return hip_fail(c, e, "build bucket-group tables");
         off[kv.first] = o;
@@ -772,14 +674,14 @@ int pvac_hip_ct_mul_plan(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_
     }
     int rc = ensure_pairs(c, A->n);
     if (rc) return rc;
-    hipError_t e = hipMemsetAsync(c->stats, 0, sizeof(plan_stats), c->stream);
+    hipError_t e = hipMemsetAsync(c->stats.get(), 0, sizeof(plan_stats), c->stream);
     if (e == hipSuccess)
-        e = launch_plan_mul(*A, *B, *C, c->pair_class, c->large_ids, c->stats, c->nb_table, kNbTableLen, c->prm.B,
+        e = launch_plan_mul(*A, *B, *C, c->pair_class.get(), c->large_ids.get(), c->stats.get(), c->nb_table.get(), kNbTableLen, c->prm.B,
                             c->stream);
     if (e == hipSuccess)
-        e = launch_exclusive_scan2_u64(C->l_off, C->e_off, A->n, c->scan_scratch, &c->totals[0], &c->totals[1], c->stream);
+        e = launch_exclusive_scan2_u64(C->l_off, C->e_off, A->n, c->scan_scratch.get(), &c->totals[0], &c->totals[1], c->stream);
     plan_stats st{};
-    if (e == hipSuccess) e = read_back(c, &st, c->stats, sizeof st);
+    if (e == hipSuccess) e = read_back(c, &st, c->stats.get(), sizeof st);
     const unsigned long long tot[2] = {st.total_layers, st.total_edges};
     if (e != hipSuccess) return hip_fail(c, e, "ct_mul_plan");
     plan->total_layer_slots = tot[0];
@@ -795,9 +697,9 @@ int pvac_hip_ct_mul_plan(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_
     if (st.n_large) {
         // shapes of the general-path pairs -> host descriptors (bucket counts from this libstdc++)
         std::vector<uint64_t> info(5 * st.n_large);
-        e = launch_gather_large(*A, *B, c->large_ids, st.n_large, c->large_info, c->stream);
+        e = launch_gather_large(*A, *B, c->large_ids.get(), st.n_large, c->large_info.get(), c->stream);
         if (e == hipSuccess)
-            e = hipMemcpyAsync(info.data(), c->large_info, info.size() * 8, hipMemcpyDeviceToHost, c->stream);
+            e = hipMemcpyAsync(info.data(), c->large_info.get(), info.size() * 8, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) return hip_fail(c, e, "ct_mul_plan (large)");
         c->large_host.resize(st.n_large);
@@ -838,12 +740,12 @@ int images_to_records(pvac_hip_ctx* c, const pvac_ct_batch* A, const std::vector
         h[pn.size() + k] = tot;
         tot += pn[k].second;
     }
-    int rc = ensure_dev(c, c->img_pairs, c->img_pairs_cap, h.size(), "alloc image pairs");
-    if (!rc) rc = ensure_dev(c, c->img_tmp, c->img_tmp_cap, 3 * std::max<uint64_t>(tot, 1), "alloc image scratch");
+    int rc = hip_fail(c, c->img_pairs.grow_floor(h.size()), "alloc image pairs");
+    if (!rc) rc = hip_fail(c, c->img_tmp.grow_floor(3 * std::max<uint64_t>(tot, 1)), "alloc image scratch");
     if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(c->img_pairs, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream);
+    hipError_t e = hipMemcpyAsync(c->img_pairs.get(), h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess)
-        e = launch_image_to_records(*A, c->img_in, c->img_pairs, (uint32_t)pn.size(), c->img_tmp, c->prm.B,
+        e = launch_image_to_records(*A, c->img_in, c->img_pairs.get(), (uint32_t)pn.size(), c->img_tmp.get(), c->prm.B,
                                     c->img_grid_y, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // h is read from the host stack
     return e == hipSuccess ? PVAC_OK : hip_fail(c, e, "chain images to records");
@@ -853,16 +755,16 @@ int images_to_records(pvac_hip_ctx* c, const pvac_ct_batch* A, const std::vector
 int run_large(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_batch* B, const uint64_t* nonces,
               pvac_ct_batch* C, uint32_t flags, uint32_t* salt_pos) {
     const size_t nl = c->large_host.size();
-    int rc = ensure_dev(c, c->desc_dev, c->desc_cap, nl, "alloc large descriptors");
-    if (!rc) rc = ensure_dev(c, c->sel_dev, c->sel_cap, nl, "alloc large descriptor order");
+    int rc = hip_fail(c, c->desc_dev.grow_floor(nl), "alloc large descriptors");
+    if (!rc) rc = hip_fail(c, c->sel_dev.grow_floor(nl), "alloc large descriptor order");
     if (rc) return rc;
     c->sel_host.resize(nl);
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 8ull << 30;
-    uint64_t budget = std::max<uint64_t>((uint64_t)(free_b / 2) / 4 + c->arena_words, 1ull << 24);
+    uint64_t budget = std::max<uint64_t>((uint64_t)(free_b / 2) / 4 + c->arena.capacity(), 1ull << 24);
     budget = std::min<uint64_t>(budget, 16ull << 30);   // <= 64 GiB of scratch per sub-batch
     // a worker of pvac_hip_ct_mul_chain shares the device with the other workers: its share
-    if (c->arena_cap_words) budget = std::min<uint64_t>(budget, std::max<uint64_t>(c->arena_cap_words, c->arena_words));
+    if (c->arena_cap_words) budget = std::min<uint64_t>(budget, std::max<uint64_t>(c->arena_cap_words, c->arena.capacity()));
     c->large_exec = c->large_host;
     size_t i = 0;
     while (i < nl) {
@@ -909,20 +811,17 @@ int run_large(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_batch* B, c
                 c->sel_host[i + q++] = (uint32_t)(k - i);
             }
         }
-        if (words > c->arena_words) {
+        if (words > c->arena.capacity()) {
             // grow with 1/8 headroom (within the budget): batches of similar pairs differ by a few
             // words, and a free + re-malloc of tens of GB stalls for seconds
             uint64_t grown = std::max<uint64_t>(words, std::min<uint64_t>(words + words / 8, budget));
             hipStreamSynchronize(c->stream);
             const auto t0 = std::chrono::steady_clock::now();
-            hipFree(c->arena);
-            c->arena = nullptr;
-            c->arena_words = 0;
-            hipError_t e = hipMalloc(&c->arena, grown * 4);
+            hipError_t e = c->arena.grow(words, grown);   // frees the old arena first
             if (e == hipErrorOutOfMemory && grown > words) {   // without the headroom
                 (void)hipGetLastError();
                 grown = words;
-                e = hipMalloc(&c->arena, grown * 4);
+                e = c->arena.grow(words, grown);
             }
             if (e == hipErrorOutOfMemory && j - i > 1) {
                 // other contexts hold the HBM the budget counted on: split this sub-batch and retry
@@ -932,32 +831,31 @@ int run_large(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_batch* B, c
                 continue;
             }
             if (e != hipSuccess) return hip_fail(c, e, "alloc ct_mul scratch arena");
-            c->arena_words = grown;
             if (std::getenv("PVAC_DEBUG_ARENA"))
                 std::fprintf(stderr, "[pvac] arena -> %.2f GB (free %.1f GB, sub-batch %zu pairs): %.1f ms\n",
                              grown * 4e-9, free_b * 1e-9, j - i,
                              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
         }
-        hipError_t e = hipMemcpyAsync(c->desc_dev + i, c->large_exec.data() + i, (j - i) * sizeof(large_desc),
+        hipError_t e = hipMemcpyAsync(c->desc_dev.get() + i, c->large_exec.data() + i, (j - i) * sizeof(large_desc),
                                       hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess)
-            e = hipMemcpyAsync(c->sel_dev + i, c->sel_host.data() + i, (j - i) * sizeof(uint32_t), hipMemcpyHostToDevice,
+            e = hipMemcpyAsync(c->sel_dev.get() + i, c->sel_host.data() + i, (j - i) * sizeof(uint32_t), hipMemcpyHostToDevice,
                                c->stream);
         if (e != hipSuccess) return hip_fail(c, e, "upload large descriptors");
         mul_large_args a{};
         a.A = *A; a.B = *B; a.C = *C;
         a.nonces = nonces;
-        a.pair_status = c->pair_status;
-        a.desc = c->desc_dev + i;
-        a.scratch = c->arena;
+        a.pair_status = c->pair_status.get();
+        a.desc = c->desc_dev.get() + i;
+        a.scratch = c->arena.get();
         a.nl = (uint32_t)(j - i);
         a.Bm = c->prm.B;
         a.canon_tag = c->prm.canon_tag;
         a.edge_budget = c->prm.edge_budget;
         a.flags = flags;
         a.salt_pos = salt_pos;
-        a.grp = c->grp;
-        a.sel = c->sel_dev + i;
+        a.grp = c->grp.get();
+        a.sel = c->sel_dev.get() + i;
         a.n_la = n_la;
         a.max_S = mS; a.max_zero = mZ; a.max_tasks = mT; a.max_capE = mE; a.max_lay = mL;
         a.max_tasks_all = mTa; a.max_la_wg = mLa; a.max_nA = mA;
@@ -966,8 +864,8 @@ int run_large(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_batch* B, c
         a.any_direct = any_dir ? 1u : 0u;
         a.all_direct = all_dir ? 1u : 0u;
         a.dir_lb = std::max<uint32_t>(mLBd, 1u);
-        a.redo_ids = c->redo_ids;
-        a.redo_cnt = c->redo_cnt;
+        a.redo_ids = c->redo_ids.get();
+        a.redo_cnt = c->redo_cnt.get();
         a.A_img = c->img_in;
         a.C_img = c->img_out;
         a.img_count = c->img_out ? c->img_count : nullptr;
@@ -991,15 +889,15 @@ int run_large(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_batch* B, c
 int redo_fresh_pairs(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_batch* B, const uint64_t* nonces,
                      pvac_ct_batch* C, uint32_t flags, uint32_t* salt_pos) {
     unsigned int cnt = 0;
-    hipError_t e = read_back(c, &cnt, c->redo_cnt, sizeof cnt);
+    hipError_t e = read_back(c, &cnt, c->redo_cnt.get(), sizeof cnt);
     if (e != hipSuccess) return hip_fail(c, e, "ct_mul_exec (redo count)");
     if (!cnt) {
         c->redo_cnt_dirty = false;
         return PVAC_OK;
     }
     std::vector<uint64_t> info(5 * (size_t)cnt);
-    e = launch_gather_large(*A, *B, c->redo_ids, cnt, c->large_info, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(info.data(), c->large_info, info.size() * 8, hipMemcpyDeviceToHost, c->stream);
+    e = launch_gather_large(*A, *B, c->redo_ids.get(), cnt, c->large_info.get(), c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(info.data(), c->large_info.get(), info.size() * 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return hip_fail(c, e, "ct_mul_exec (redo shapes)");
     std::vector<large_desc> redo(cnt);
@@ -1064,12 +962,12 @@ int pvac_hip_ct_mul_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_
         return fail(c, PVAC_EINVAL, "ct_mul_exec: WITH_SIGMA needs salts, C->sigma and H");
     uint32_t* salt_pos = nullptr;
     if (with_sigma) {
-        int rc = ensure_dev(c, c->salt_pos, c->salt_cap, plan->total_edge_slots, "alloc salt positions");
+        int rc = hip_fail(c, c->salt_pos.grow_floor(plan->total_edge_slots), "alloc salt positions");
         if (rc) return rc;
-        salt_pos = c->salt_pos;
+        salt_pos = c->salt_pos.get();
     }
     if (c->redo_cnt_dirty) {   // a read-back of zero leaves it clean: no memset per exec
-        const hipError_t e = hipMemsetAsync(c->redo_cnt, 0, sizeof(unsigned int), c->stream);
+        const hipError_t e = hipMemsetAsync(c->redo_cnt.get(), 0, sizeof(unsigned int), c->stream);
         if (e != hipSuccess) return hip_fail(c, e, "reset redo count");
     }
     c->redo_cnt_dirty = true;   // until this exec reads back a zero count
@@ -1078,15 +976,15 @@ int pvac_hip_ct_mul_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_
         mul_fresh_args a;
         std::memset(&a, 0, sizeof a);   // padding too: the upload below is skipped on equal bytes
         a.A = *A; a.B = *B; a.C = *C;
-        a.recs = c->fresh_recs;
+        a.recs = c->fresh_recs.get();
         a.nonces = nonces;
-        a.pair_class = c->pair_class;
-        a.pair_status = c->pair_status;
-        a.nb_table = c->nb_table;
-        a.nb_magic = c->nb_magic;
+        a.pair_class = c->pair_class.get();
+        a.pair_status = c->pair_status.get();
+        a.nb_table = c->nb_table.get();
+        a.nb_magic = c->nb_magic.get();
         a.salt_pos = salt_pos;
-        a.redo_ids = c->redo_ids;
-        a.redo_cnt = c->redo_cnt;
+        a.redo_ids = c->redo_ids.get();
+        a.redo_cnt = c->redo_cnt.get();
         a.canon_tag = c->prm.canon_tag;
         a.edge_budget = c->prm.edge_budget;
         a.Bm = c->prm.B;
@@ -1102,22 +1000,19 @@ int pvac_hip_ct_mul_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_
             hipError_t e = launch_mul_layers_fresh(a, c->stream);
             if (e != hipSuccess) return hip_fail(c, e, "mul_layers_fresh");
         }
-        if (!c->fresh_args) {
-            hipError_t ea = hipMalloc(&c->fresh_args, sizeof(mul_fresh_args));
-            if (ea != hipSuccess) return hip_fail(c, ea, "alloc fresh args");
-        }
+        if (const hipError_t ea = c->fresh_args.grow(1, 1)) return hip_fail(c, ea, "alloc fresh args");
         // stream-ordered copy from the ctx's host mirror (kept alive until the next exec); a batch
         // exec'd again into the same buffers (the kernels never write their arguments) reuses it
         hipError_t e = hipSuccess;
         if (!c->fresh_args_uploaded || std::memcmp(&c->fresh_args_host, &a, sizeof a) != 0) {
             c->fresh_args_uploaded = false;
             std::memcpy(&c->fresh_args_host, &a, sizeof a);
-            e = hipMemcpyAsync(c->fresh_args, &c->fresh_args_host, sizeof a, hipMemcpyHostToDevice, c->stream);
+            e = hipMemcpyAsync(c->fresh_args.get(), &c->fresh_args_host, sizeof a, hipMemcpyHostToDevice, c->stream);
             c->fresh_args_uploaded = e == hipSuccess;
         }
         if (e != hipSuccess) return hip_fail(c, e, "upload fresh args");
         scoped_timer t(c, "ct_mul_fresh");
-        e = launch_ct_mul_fresh(a, c->fresh_args, c->num_cus, c->stream);
+        e = launch_ct_mul_fresh(a, c->fresh_args.get(), c->num_cus, c->stream);
         if (e != hipSuccess) return hip_fail(c, e, "ct_mul_fresh");
     }
     if (plan->n_large && (flags & PVAC_MUL_ORDER_CANONICAL) &&
@@ -1188,13 +1083,13 @@ int pvac_hip_ct_add_plan(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_
     c->merge_host.clear();
     // as in ct_mul_plan: earlier plans go stale now, this one is stamped only once it has succeeded
     const uint32_t stamp = ++c->plan_stamp;
-    hipError_t e = hipMemsetAsync(c->stats, 0, sizeof(plan_stats), c->stream);
+    hipError_t e = hipMemsetAsync(c->stats.get(), 0, sizeof(plan_stats), c->stream);
     if (e == hipSuccess)
-        e = launch_plan_add(*A, *B, *C, c->stats, c->pair_class, c->large_ids, c->prm.edge_budget, c->stream);
+        e = launch_plan_add(*A, *B, *C, c->stats.get(), c->pair_class.get(), c->large_ids.get(), c->prm.edge_budget, c->stream);
     if (e == hipSuccess)
-        e = launch_exclusive_scan2_u64(C->l_off, C->e_off, A->n, c->scan_scratch, &c->totals[0], &c->totals[1], c->stream);
+        e = launch_exclusive_scan2_u64(C->l_off, C->e_off, A->n, c->scan_scratch.get(), &c->totals[0], &c->totals[1], c->stream);
     plan_stats st{};
-    if (e == hipSuccess) e = read_back(c, &st, c->stats, sizeof st);
+    if (e == hipSuccess) e = read_back(c, &st, c->stats.get(), sizeof st);
     const unsigned long long tot[2] = {st.total_layers, st.total_edges};
     if (e != hipSuccess) return hip_fail(c, e, "ct_add_plan");
     plan->total_layer_slots = tot[0];
@@ -1204,9 +1099,9 @@ int pvac_hip_ct_add_plan(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_
     plan->n_small = A->n - st.n_large;
     if (st.n_large) {   // guard_budget pairs: shapes and offsets for the per-pair merge launches
         std::vector<uint64_t> info(8 * st.n_large);
-        e = launch_gather_merge(*A, *B, *C, c->large_ids, st.n_large, c->large_info, c->stream);
+        e = launch_gather_merge(*A, *B, *C, c->large_ids.get(), st.n_large, c->large_info.get(), c->stream);
         if (e == hipSuccess)
-            e = hipMemcpyAsync(info.data(), c->large_info, info.size() * 8, hipMemcpyDeviceToHost, c->stream);
+            e = hipMemcpyAsync(info.data(), c->large_info.get(), info.size() * 8, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) return hip_fail(c, e, "ct_add_plan (merge)");
         for (uint64_t k = 0; k < st.n_large; ++k) {
@@ -1246,30 +1141,20 @@ int pvac_hip_ct_add_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_
         scoped_timer t(c, "ct_add");
         const int rc = hip_fail(c,
                                 launch_ct_add(*A, *B, *C, negate_b, plan->max_layers,
-                                              plan->n_large ? c->pair_class : nullptr, c->stream),
+                                              plan->n_large ? c->pair_class.get() : nullptr, c->stream),
                                 "ct_add");
         if (rc) return rc;
     }
     if (!plan->n_large) return PVAC_OK;
     // guard_budget (encrypt.hpp:106-111): compact_edges + compact_layers per over-budget pair
     scoped_timer t(c, "ct_add_merge");
-    if (!c->merge_counters) {
-        hipError_t e = hipMalloc(&c->merge_counters, 2 * sizeof(unsigned long long));
-        if (e != hipSuccess) return hip_fail(c, e, "alloc merge counters");
-    }
+    if (const hipError_t e = c->merge_counters.grow(2, 2)) return hip_fail(c, e, "alloc merge counters");
     for (const merge_pair_info& m : c->merge_host) {
         const size_t need = merge_scratch_bytes(m.nA + m.nB, m.L);
-        if (need > c->merge_cap) {
-            hipFree(c->merge_scratch);
-            c->merge_scratch = nullptr;
-            c->merge_cap = 0;
-            hipError_t e = hipMalloc(&c->merge_scratch, need);
-            if (e != hipSuccess) return hip_fail(c, e, "alloc merge scratch");
-            c->merge_cap = need;
-        }
+        if (const hipError_t e = c->merge_scratch.grow(need, need)) return hip_fail(c, e, "alloc merge scratch");
         const int rc = hip_fail(c,
-                                launch_add_merge(*A, *B, *C, m.pair, m, c->prm.B, negate_b, c->merge_scratch,
-                                                 c->merge_cap, c->merge_counters, c->stream),
+                                launch_add_merge(*A, *B, *C, m.pair, m, c->prm.B, negate_b, c->merge_scratch.get(),
+                                                 c->merge_scratch.capacity(), c->merge_counters.get(), c->stream),
                                 "ct_add merge");
         if (rc) return rc;
     }
@@ -1340,12 +1225,11 @@ int pvac_hip_ctx_set_secret(pvac_hip_ctx* c, const uint64_t prf_k[4], const uint
     if (lpn_n == 0 || words > 64 || tau_den == 0 || tau_num > tau_den)
         return fail(c, PVAC_EINVAL, "set_secret: lpn_n must be in [1, 4096], 0 <= tau_num <= tau_den, tau_den > 0");
     if (lpn_t < 127) return fail(c, PVAC_ENOSYS, "set_secret: lpn_t < 127 not supported");
-    hipFree(c->lpn_s);
-    c->lpn_s = nullptr;
+    c->lpn_s.release();
     c->have_secret = false;
-    hipError_t e = hipMalloc(&c->lpn_s, 64 * 8);
-    if (e == hipSuccess) e = hipMemset(c->lpn_s, 0, 64 * 8);
-    if (e == hipSuccess) e = hipMemcpy(c->lpn_s, lpn_s_host, (size_t)words * 8, hipMemcpyHostToDevice);
+    hipError_t e = c->lpn_s.grow(64, 64);
+    if (e == hipSuccess) e = hipMemset(c->lpn_s.get(), 0, 64 * 8);
+    if (e == hipSuccess) e = hipMemcpy(c->lpn_s.get(), lpn_s_host, (size_t)words * 8, hipMemcpyHostToDevice);
     if (e != hipSuccess) return hip_fail(c, e, "set_secret");
     std::memcpy(c->prf_k, prf_k, 32);
     c->lpn_words = words;
@@ -1399,7 +1283,7 @@ int prf_setup(pvac_hip_ctx* c, prf_consts& k) {
                                         "pvac.prf.noise.1", "pvac.prf.noise.2", "pvac.prf.noise.3"};
     for (int d = 0; d < 6; ++d) k.dom_hash[d] = fnv1a(doms[d]);
     k.toep_hash = fnv1a("pvac.dom.toeplitz");
-    k.s_bits = c->lpn_s;
+    k.s_bits = c->lpn_s.get();
     k.s_words = c->lpn_words;
     k.tau_num = c->tau_num;
     k.tau_den = c->tau_den;
@@ -1407,9 +1291,9 @@ int prf_setup(pvac_hip_ctx* c, prf_consts& k) {
 }
 
 int ensure_prf_scratch(pvac_hip_ctx* c, uint64_t cores) {
-    int rc = ensure_dev(c, c->prf_req, c->prf_req_cap, cores * prf_request_bytes(), "alloc prf requests");
+    int rc = hip_fail(c, c->prf_req.grow_floor(cores * prf_request_bytes()), "alloc prf requests");
     if (rc) return rc;
-    return ensure_dev(c, c->prf_core, c->prf_core_cap, 2 * cores, "alloc prf cores");
+    return hip_fail(c, c->prf_core.grow_floor(2 * cores), "alloc prf cores");
 }
 
 }  // namespace
@@ -1423,7 +1307,7 @@ int pvac_hip_prf(pvac_hip_ctx* c, int kind, size_t n, const uint64_t* seeds, uin
     rc = ensure_prf_scratch(c, 3 * (uint64_t)n);
     if (rc) return rc;
     scoped_timer t(c, "prf");
-    return hip_fail(c, launch_prf(k, kind, seeds, n, c->prf_req, c->prf_core, out, c->stream), "prf");
+    return hip_fail(c, launch_prf(k, kind, seeds, n, c->prf_req.get(), c->prf_core.get(), out, c->stream), "prf");
 }
 
 // ---------------------------------------------------------------- enc_value
@@ -1474,7 +1358,7 @@ int pvac_hip_enc_value_depth(pvac_hip_ctx* c, size_t n, const uint64_t* values, 
     const bool with_sigma = (flags & PVAC_ENC_WITH_SIGMA) != 0;
     if (with_sigma && (!C->sigma || !c->H.ready || C->sigma_words != c->prm.m_bits / 64))
         return fail(c, PVAC_EINVAL, "enc_value: WITH_SIGMA needs C->sigma (m_bits/64 words per edge) and H");
-    if (!c->powg) return fail(c, PVAC_EINVAL, "enc_value: powg_B not set (pvac_hip_ctx_set_powg)");
+    if (!c->powg.get()) return fail(c, PVAC_EINVAL, "enc_value: powg_B not set (pvac_hip_ctx_set_powg)");
     C->n = n;
     if (!n) return PVAC_OK;
     prf_consts k{};
@@ -1488,7 +1372,7 @@ int pvac_hip_enc_value_depth(pvac_hip_ctx* c, size_t n, const uint64_t* values, 
     plan_noise(c, depth_hint, a.Z2, a.Z3);
     a.n = n;
     a.canon = c->prm.canon_tag;
-    a.powg = c->powg;
+    a.powg = c->powg.get();
     const uint32_t npre = 8 + 2 * a.Z2 + 3 * a.Z3;
     if ((uint64_t)8 + 2ull * a.Z2 + 3ull * a.Z3 > kEncPreMax)
         return fail(c, PVAC_ENOSYS, "enc_value: noise plan beyond 256 pre-merge edges per half (depth hint > 124 with the default Params)");
@@ -1504,15 +1388,8 @@ int pvac_hip_enc_value_depth(pvac_hip_ctx* c, size_t n, const uint64_t* values, 
     const uint64_t off_e = off_lay + al((uint64_t)n * 2 * sizeof(pvac_layer));
     const uint64_t off_sig = off_e + al(pe * 32);
     const uint64_t total = off_sig + (with_sigma ? al(pe * sw * 8) : 0);
-    if (total > c->enc_arena_cap) {
-        hipFree(c->enc_arena);
-        c->enc_arena = nullptr;
-        c->enc_arena_cap = 0;
-        hipError_t e = hipMalloc(&c->enc_arena, total);
-        if (e != hipSuccess) return hip_fail(c, e, "alloc enc scratch");
-        c->enc_arena_cap = total;
-    }
-    uint8_t* A = c->enc_arena;
+    if (const hipError_t ea = c->enc_arena.grow(total, total)) return hip_fail(c, ea, "alloc enc scratch");
+    uint8_t* A = c->enc_arena.get();
     pvac_ct_batch pre{};
     pre.n = n;
     pre.l_off = (uint64_t*)(A + off_csr);
@@ -1555,7 +1432,7 @@ int pvac_hip_base_R(pvac_hip_ctx* c, const pvac_ct_batch* X, uint64_t* R_out) {
     rc = ensure_prf_scratch(c, 4 * slots);   // 3 cores per slot + the BASE flags behind them
     if (rc) return rc;
     scoped_timer t(c, "base_R");
-    return hip_fail(c, launch_base_R(k, *X, slots, c->prf_req, c->prf_core, R_out, c->stream), "base_R");
+    return hip_fail(c, launch_base_R(k, *X, slots, c->prf_req.get(), c->prf_core.get(), R_out, c->stream), "base_R");
 }
 
 // ---------------------------------------------------------------- measured ALU ceilings
@@ -1577,25 +1454,24 @@ int pvac_hip_check_mul_gsum(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_
     if (!c || !n_bad || !batch_ok(A) || !batch_ok(B) || !batch_ok(C) || !nonces)
         return fail(c, PVAC_EINVAL, "check_mul_gsum: bad arguments");
     if (A->n != B->n || A->n != C->n) return fail(c, PVAC_EINVAL, "check_mul_gsum: batch sizes differ");
-    if (!c->powg) return fail(c, PVAC_EINVAL, "check_mul_gsum: powg_B not set (pvac_hip_ctx_set_powg)");
+    if (!c->powg.get()) return fail(c, PVAC_EINVAL, "check_mul_gsum: powg_B not set (pvac_hip_ctx_set_powg)");
     *n_bad = 0;
     if (!A->n) return PVAC_OK;
-    hipError_t e = hipSuccess;
-    if (!c->check_buf) e = hipMalloc(&c->check_buf, 32);
-    if (e == hipSuccess) e = hipMemsetAsync(c->check_buf, 0, 32, c->stream);
-    if (e == hipSuccess) e = launch_check_sizes(*A, *B, *C, c->check_buf, c->stream);
+    hipError_t e = c->check_buf.grow(8, 8);
+    if (e == hipSuccess) e = hipMemsetAsync(c->check_buf.get(), 0, 32, c->stream);
+    if (e == hipSuccess) e = launch_check_sizes(*A, *B, *C, c->check_buf.get(), c->stream);
     unsigned int mx[4] = {0, 0, 0, 0};
-    if (e == hipSuccess) e = hipMemcpyAsync(mx, c->check_buf, sizeof mx, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(mx, c->check_buf.get(), sizeof mx, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return hip_fail(c, e, "check_mul_gsum (sizes)");
-    unsigned long long* cnt = (unsigned long long*)(c->check_buf + 4);
+    unsigned long long* cnt = (unsigned long long*)(c->check_buf.get() + 4);
     // layer tables beyond one workgroup's LDS (chain depth 9 on): per-workgroup slabs in global memory
     const uint64_t gs = check_gsum_scratch_bytes(c->prm.B, mx, A->n, c->num_cus);
     if (gs) {
-        const int rc = ensure_dev(c, c->check_scratch, c->check_scratch_cap, (size_t)gs, "alloc gsum check scratch");
+        const int rc = hip_fail(c, c->check_scratch.grow_floor((size_t)gs), "alloc gsum check scratch");
         if (rc) return rc;
     }
-    e = launch_check_gsum(*A, *B, *C, nonces, c->powg, c->prm.B, mx, status, cnt, c->num_cus, gs ? c->check_scratch : nullptr,
+    e = launch_check_gsum(*A, *B, *C, nonces, c->powg.get(), c->prm.B, mx, status, cnt, c->num_cus, gs ? c->check_scratch.get() : nullptr,
                           c->stream);
     if (e == hipErrorInvalidValue) return fail(c, PVAC_ERANGE, "check_mul_gsum: no scratch for the layer tables");
     unsigned long long bad = 0;
@@ -1609,11 +1485,10 @@ int pvac_hip_check_mul_gsum(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_
 // ---------------------------------------------------------------- dec_value
 int pvac_hip_ctx_set_powg(pvac_hip_ctx* c, const uint64_t* powg_host, uint32_t count) {
     if (!c || !powg_host || count < c->prm.B) return fail(c, PVAC_EINVAL, "set_powg: need B (lo, hi) pairs");
-    hipFree(c->powg);
-    c->powg = nullptr;
+    c->powg.release();
     c->powg_n = 0;
-    hipError_t e = hipMalloc(&c->powg, (size_t)count * 16);
-    if (e == hipSuccess) e = hipMemcpy(c->powg, powg_host, (size_t)count * 16, hipMemcpyHostToDevice);
+    hipError_t e = c->powg.grow(2 * (size_t)count, 2 * (size_t)count);
+    if (e == hipSuccess) e = hipMemcpy(c->powg.get(), powg_host, (size_t)count * 16, hipMemcpyHostToDevice);
     if (e != hipSuccess) return hip_fail(c, e, "set_powg");
     c->powg_n = count;
     return PVAC_OK;
@@ -1622,31 +1497,25 @@ int pvac_hip_ctx_set_powg(pvac_hip_ctx* c, const uint64_t* powg_host, uint32_t c
 int pvac_hip_dec_value(pvac_hip_ctx* c, const pvac_ct_batch* X, const uint64_t* R_base, uint64_t* out,
                        uint32_t* status) {
     if (!c || !batch_ok(X) || !out || !status || (X->n && !R_base)) return fail(c, PVAC_EINVAL, "dec_value: arguments");
-    if (!c->powg) return fail(c, PVAC_EINVAL, "dec_value: powg_B not set (pvac_hip_ctx_set_powg)");
+    if (!c->powg.get()) return fail(c, PVAC_EINVAL, "dec_value: powg_B not set (pvac_hip_ctx_set_powg)");
     if (!X->n) return PVAC_OK;
     int rc = ensure_pairs(c, X->n);
     if (rc) return rc;
-    rc = ensure_dev(c, c->dec_roff, c->dec_roff_cap, X->n, "alloc dec offsets");
+    rc = hip_fail(c, c->dec_roff.grow_floor(X->n), "alloc dec offsets");
     if (rc) return rc;
     // dense per-cipher layer offsets (the batch may be capacity-padded)
-    hipError_t e = hipMemcpyAsync(c->dec_roff, X->l_cnt, X->n * 8, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = launch_exclusive_scan_u64(c->dec_roff, X->n, c->scan_scratch, &c->totals[0], c->stream);
+    hipError_t e = hipMemcpyAsync(c->dec_roff.get(), X->l_cnt, X->n * 8, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = launch_exclusive_scan_u64(c->dec_roff.get(), X->n, c->scan_scratch.get(), &c->totals[0], c->stream);
     unsigned long long total = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&total, &c->totals[0], 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return hip_fail(c, e, "dec_value (offsets)");
     const size_t need = dec_scratch_bytes(total);
-    if (need > c->dec_cap) {
-        hipFree(c->dec_scratch);
-        c->dec_scratch = nullptr;
-        c->dec_cap = 0;
-        e = hipMalloc(&c->dec_scratch, need);
-        if (e != hipSuccess) return hip_fail(c, e, "alloc dec scratch");
-        c->dec_cap = need;
-    }
+    e = c->dec_scratch.grow(need, need);
+    if (e != hipSuccess) return hip_fail(c, e, "alloc dec scratch");
     scoped_timer t(c, "dec_value");
     return hip_fail(c,
-                    launch_dec_value(*X, R_base, c->powg, c->prm.B, c->dec_roff, total, c->dec_scratch, out, status,
+                    launch_dec_value(*X, R_base, c->powg.get(), c->prm.B, c->dec_roff.get(), total, c->dec_scratch.get(), out, status,
                                      c->stream),
                     "dec_value");
 }
@@ -1708,7 +1577,7 @@ int pvac_hip_batch_pack(pvac_hip_ctx* c, const pvac_ct_batch* src, pvac_ct_batch
     if (e == hipSuccess) e = hipMemcpyAsync(dst->l_off, src->l_cnt, n * 8, hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dst->e_off, src->e_cnt, n * 8, hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess)
-        e = launch_exclusive_scan2_u64(dst->l_off, dst->e_off, n, c->scan_scratch, &c->totals[0], &c->totals[1],
+        e = launch_exclusive_scan2_u64(dst->l_off, dst->e_off, n, c->scan_scratch.get(), &c->totals[0], &c->totals[1],
                                        c->stream);
     unsigned long long tot[2] = {0, 0};
     if (e == hipSuccess) e = read_back(c, tot, c->totals, sizeof tot);
@@ -1722,25 +1591,6 @@ int pvac_hip_batch_pack(pvac_hip_ctx* c, const pvac_ct_batch* src, pvac_ct_batch
 }  // extern "C"
 
 namespace {
-
-// grows a stream-ordered device array to at least `need` elements (1/8 headroom); contents are lost
-template <typename T>
-hipError_t grow_async(T*& p, size_t& cap, size_t need, hipStream_t st) {
-    if (need <= cap && p) return hipSuccess;
-    if (p) hipFreeAsync(p, st);
-    p = nullptr;
-    cap = 0;
-    const size_t want = std::max<size_t>(need + need / 8, 64);
-    hipError_t e = hipMallocAsync((void**)&p, want * sizeof(T), st);
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        e = hipMallocAsync((void**)&p, std::max<size_t>(need, 64) * sizeof(T), st);
-        if (e == hipSuccess) cap = std::max<size_t>(need, 64);
-    } else if (e == hipSuccess) {
-        cap = want;
-    }
-    return e;
-}
 
 struct chain_range {
     uint64_t end = 0;               // last input (exclusive) of this device range
@@ -1793,48 +1643,37 @@ bool stage_chunk(pvac_hip_ctx* k, chain_shared* sh, const pvac_ct_batch& src, pv
                    std::string("ct_mul_chain: stage ") + where + ": " + hipGetErrorString(e));
         return false;
     };
-    if (kk > S.n_cap) {
-        size_t c1 = S.n_cap, c2 = S.n_cap, c3 = S.n_cap, c4 = S.n_cap;
-        if (!hipchk(grow_async(S.l_off, c1, kk, k->stream), "alloc") || !hipchk(grow_async(S.l_cnt, c2, kk, k->stream), "alloc") ||
-            !hipchk(grow_async(S.e_off, c3, kk, k->stream), "alloc") || !hipchk(grow_async(S.e_cnt, c4, kk, k->stream), "alloc"))
-            return false;
-        S.n_cap = std::min(std::min(c1, c2), std::min(c3, c4));
-    }
+    for (dev_stream_buf<uint64_t>* b : {&S.l_off, &S.l_cnt, &S.e_off, &S.e_cnt})
+        if (!hipchk(b->grow_headroom(kk, k->stream), "alloc")) return false;
     if (ensure_pairs(k, kk)) {
         sh->failed(PVAC_ENOMEM, "ct_mul_chain: stage scratch: " + k->err);
         return false;
     }
     const int sd = sh->x_dev, dd = k->device;
-    if (!hipchk(hipMemcpyPeerAsync(S.l_cnt, dd, src.l_cnt, sd, kk * 8, k->stream), "counts") ||
-        !hipchk(hipMemcpyPeerAsync(S.e_cnt, dd, src.e_cnt, sd, kk * 8, k->stream), "counts") ||
-        !hipchk(hipMemcpyAsync(S.l_off, S.l_cnt, kk * 8, hipMemcpyDeviceToDevice, k->stream), "offsets") ||
-        !hipchk(hipMemcpyAsync(S.e_off, S.e_cnt, kk * 8, hipMemcpyDeviceToDevice, k->stream), "offsets") ||
-        !hipchk(launch_exclusive_scan_u64(S.l_off, kk, k->scan_scratch, &k->totals[0], k->stream), "scan") ||
-        !hipchk(launch_exclusive_scan_u64(S.e_off, kk, k->scan_scratch, &k->totals[1], k->stream), "scan"))
+    if (!hipchk(hipMemcpyPeerAsync(S.l_cnt.get(), dd, src.l_cnt, sd, kk * 8, k->stream), "counts") ||
+        !hipchk(hipMemcpyPeerAsync(S.e_cnt.get(), dd, src.e_cnt, sd, kk * 8, k->stream), "counts") ||
+        !hipchk(hipMemcpyAsync(S.l_off.get(), S.l_cnt.get(), kk * 8, hipMemcpyDeviceToDevice, k->stream), "offsets") ||
+        !hipchk(hipMemcpyAsync(S.e_off.get(), S.e_cnt.get(), kk * 8, hipMemcpyDeviceToDevice, k->stream), "offsets") ||
+        !hipchk(launch_exclusive_scan_u64(S.l_off.get(), kk, k->scan_scratch.get(), &k->totals[0], k->stream), "scan") ||
+        !hipchk(launch_exclusive_scan_u64(S.e_off.get(), kk, k->scan_scratch.get(), &k->totals[1], k->stream), "scan"))
         return false;
     unsigned long long tot[2] = {0, 0};
     if (!hipchk(hipMemcpyAsync(tot, k->totals, sizeof tot, hipMemcpyDeviceToHost, k->stream), "totals") ||
         !hipchk(hipStreamSynchronize(k->stream), "totals"))
         return false;
-    if (tot[0] > S.l_cap && !hipchk(grow_async(S.layers, S.l_cap, tot[0], k->stream), "alloc layers")) return false;
-    if (tot[1] > S.e_cap) {
-        size_t c1 = S.e_cap, c2 = S.e_cap, c3 = S.e_cap;
-        if (!hipchk(grow_async(S.meta, c1, tot[1], k->stream), "alloc edges") ||
-            !hipchk(grow_async(S.w_lo, c2, tot[1], k->stream), "alloc edges") ||
-            !hipchk(grow_async(S.w_hi, c3, tot[1], k->stream), "alloc edges"))
-            return false;
-        S.e_cap = std::min(c1, std::min(c2, c3));
-    }
+    if (!hipchk(S.layers.grow_headroom(tot[0], k->stream), "alloc layers")) return false;
+    for (dev_stream_buf<uint64_t>* b : {&S.meta, &S.w_lo, &S.w_hi})
+        if (!hipchk(b->grow_headroom(tot[1], k->stream), "alloc edges")) return false;
     out = pvac_ct_batch{};
     out.n = kk;
-    out.l_off = S.l_off;
-    out.l_cnt = S.l_cnt;
-    out.layers = S.layers;
-    out.e_off = S.e_off;
-    out.e_cnt = S.e_cnt;
-    out.meta = S.meta;
-    out.w_lo = S.w_lo;
-    out.w_hi = S.w_hi;
+    out.l_off = S.l_off.get();
+    out.l_cnt = S.l_cnt.get();
+    out.layers = S.layers.get();
+    out.e_off = S.e_off.get();
+    out.e_cnt = S.e_cnt.get();
+    out.meta = S.meta.get();
+    out.w_lo = S.w_lo.get();
+    out.w_hi = S.w_hi.get();
     return hipchk(launch_stage_rows(src, out, k->stream), "rows");
 }
 
@@ -1854,37 +1693,30 @@ bool chain_final_sigma(pvac_hip_ctx* k, chain_shared* sh, uint32_t d, uint64_t c
     };
     const uint64_t slots = std::max<uint64_t>(plan.total_edge_slots, 1);
     const uint32_t sw = k->prm.m_bits / 64;
-    if (slots > S.s_cap) {
-        if (S.sigma) hipFreeAsync(S.sigma, k->stream);
-        S.sigma = nullptr;
-        S.s_cap = 0;
-        if (!hipchk(hipMallocAsync((void**)&S.sigma, slots * sw * 8, k->stream), "alloc (1 KiB per edge: a smaller chunk?)"))
-            return false;
-        S.s_cap = slots;
-    }
-    if (!hipchk(grow_async(k->chain_salts, k->chain_salt_cap, slots, k->stream), "alloc salts")) return false;
+    if (!hipchk(S.sigma.grow(slots * sw, slots * sw, k->stream), "alloc (1 KiB per edge: a smaller chunk?)")) return false;
+    if (!hipchk(k->chain_salts.grow_headroom(slots, k->stream), "alloc salts")) return false;
     if (o.salts_at) {
-        if (o.salts_at(o.user, d, c0, &A, &Xv, &C, k->chain_salts, plan.total_edge_slots, (void*)k->stream) != 0) {
+        if (o.salts_at(o.user, d, c0, &A, &Xv, &C, k->chain_salts.get(), plan.total_edge_slots, (void*)k->stream) != 0) {
             sh->failed(PVAC_EINVAL, "ct_mul_chain: salts_at callback failed");
             return false;
         }
-    } else if (!hipchk(launch_fill_random(o.nonce_seed ^ 0x5A175A175A175A17ull ^ (97ull * c0 + d), k->chain_salts, slots,
+    } else if (!hipchk(launch_fill_random(o.nonce_seed ^ 0x5A175A175A175A17ull ^ (97ull * c0 + d), k->chain_salts.get(), slots,
                                           k->stream),
                        "fill salts")) {
         return false;
     }
-    C.sigma = S.sigma;
+    C.sigma = S.sigma.get();
     C.sigma_words = sw;
     bool hash_order = (mflags & PVAC_MUL_ORDER_CANONICAL) == 0;
     if (hash_order) {
         std::vector<uint32_t> stv(C.n);
-        if (!hipchk(hipMemcpyAsync(stv.data(), k->pair_status, C.n * 4, hipMemcpyDeviceToHost, k->stream), "status") ||
+        if (!hipchk(hipMemcpyAsync(stv.data(), k->pair_status.get(), C.n * 4, hipMemcpyDeviceToHost, k->stream), "status") ||
             !hipchk(hipStreamSynchronize(k->stream), "status"))
             return false;
         for (uint32_t v : stv) hash_order &= v != 1u;
     }
-    if (hash_order) return hipchk(launch_sigma(k->H, k->prm, C, k->chain_salts, nullptr, k->num_cus, k->stream), "launch");
-    if (pvac_hip_ct_mul_exec(k, &plan, &A, &Xv, k->chain_nonces, k->chain_salts, &C, mflags | PVAC_MUL_WITH_SIGMA)) {
+    if (hash_order) return hipchk(launch_sigma(k->H, k->prm, C, k->chain_salts.get(), nullptr, k->num_cus, k->stream), "launch");
+    if (pvac_hip_ct_mul_exec(k, &plan, &A, &Xv, k->chain_nonces.get(), k->chain_salts.get(), &C, mflags | PVAC_MUL_WITH_SIGMA)) {
         sh->failed(PVAC_EDEVICE, "ct_mul_chain: sigma exec: " + k->err);
         return false;
     }
@@ -1945,82 +1777,71 @@ void chain_worker(pvac_hip_ctx* k, chain_shared* sh, chain_range* rg, bool stage
                     return;
             }
             chain_set& S = k->chain_bufs[cur];
-            if (kk > S.n_cap) {
-                size_t c1 = S.n_cap, c2 = S.n_cap, c3 = S.n_cap, c4 = S.n_cap;
-                if (!hipchk(grow_async(S.l_off, c1, kk, k->stream), "alloc offsets") ||
-                    !hipchk(grow_async(S.l_cnt, c2, kk, k->stream), "alloc counts") ||
-                    !hipchk(grow_async(S.e_off, c3, kk, k->stream), "alloc offsets") ||
-                    !hipchk(grow_async(S.e_cnt, c4, kk, k->stream), "alloc counts"))
-                    return;
-                S.n_cap = std::min(std::min(c1, c2), std::min(c3, c4));
-            }
+            if (!hipchk(S.l_off.grow_headroom(kk, k->stream), "alloc offsets") ||
+                !hipchk(S.l_cnt.grow_headroom(kk, k->stream), "alloc counts") ||
+                !hipchk(S.e_off.grow_headroom(kk, k->stream), "alloc offsets") ||
+                !hipchk(S.e_cnt.grow_headroom(kk, k->stream), "alloc counts"))
+                return;
             pvac_ct_batch C{};
             C.n = kk;
-            C.l_off = S.l_off;
-            C.l_cnt = S.l_cnt;
-            C.e_off = S.e_off;
-            C.e_cnt = S.e_cnt;
+            C.l_off = S.l_off.get();
+            C.l_cnt = S.l_cnt.get();
+            C.e_off = S.e_off.get();
+            C.e_cnt = S.e_cnt.get();
             pvac_hip_plan plan{};
             if (!rcchk(pvac_hip_ct_mul_plan(k, &A, &Xv, &C, &plan), "plan")) return;
             // an output array that does not fit first takes this worker's scratch arena back (the
             // general path reallocates it within what is left, splitting its sub-batch if needed)
-            auto grow_out = [&](auto*& p, size_t& cap, size_t need, const char* what) -> bool {
-                hipError_t e = grow_async(p, cap, need, k->stream);
-                if (e == hipErrorOutOfMemory && k->arena) {
+            auto grow_out = [&](auto& b, size_t need, const char* what) -> bool {
+                hipError_t e = b.grow_headroom(need, k->stream);
+                if (e == hipErrorOutOfMemory && k->arena.get()) {
                     (void)hipGetLastError();
                     e = hipStreamSynchronize(k->stream);
-                    hipFree(k->arena);
-                    k->arena = nullptr;
-                    k->arena_words = 0;
-                    if (e == hipSuccess) e = grow_async(p, cap, need, k->stream);
+                    k->arena.release();
+                    if (e == hipSuccess) e = b.grow_headroom(need, k->stream);
                 }
                 return hipchk(e, what);
             };
-            if (plan.total_layer_slots > S.l_cap && !grow_out(S.layers, S.l_cap, plan.total_layer_slots, "alloc layers"))
+            if (!grow_out(S.layers, plan.total_layer_slots, "alloc layers") ||
+                !grow_out(S.meta, plan.total_edge_slots, "alloc edges") ||
+                !grow_out(S.w_lo, plan.total_edge_slots, "alloc edges") ||
+                !grow_out(S.w_hi, plan.total_edge_slots, "alloc edges"))
                 return;
-            if (plan.total_edge_slots > S.e_cap) {
-                size_t c1 = S.e_cap, c2 = S.e_cap, c3 = S.e_cap;
-                if (!grow_out(S.meta, c1, plan.total_edge_slots, "alloc edges") ||
-                    !grow_out(S.w_lo, c2, plan.total_edge_slots, "alloc edges") ||
-                    !grow_out(S.w_hi, c3, plan.total_edge_slots, "alloc edges"))
-                    return;
-                S.e_cap = std::min(c1, std::min(c2, c3));
-            }
             const size_t nw = 2 * std::max<uint64_t>(plan.total_layer_slots, 1);
-            if (!hipchk(grow_async(k->chain_nonces, k->chain_nonce_cap, nw, k->stream), "alloc nonces")) return;
-            C.layers = S.layers;
-            C.meta = S.meta;
-            C.w_lo = S.w_lo;
-            C.w_hi = S.w_hi;
+            if (!hipchk(k->chain_nonces.grow_headroom(nw, k->stream), "alloc nonces")) return;
+            C.layers = S.layers.get();
+            C.meta = S.meta.get();
+            C.w_lo = S.w_lo.get();
+            C.w_hi = S.w_hi.get();
             if (o.nonces_at) {
-                if (o.nonces_at(o.user, d, c0, &A, &Xv, &C, k->chain_nonces, nw, (void*)k->stream) != 0) {
+                if (o.nonces_at(o.user, d, c0, &A, &Xv, &C, k->chain_nonces.get(), nw, (void*)k->stream) != 0) {
                     sh->failed(PVAC_EINVAL, "ct_mul_chain: nonces_at callback failed");
                     return;
                 }
             } else if (o.fill_nonces) {
-                if (o.fill_nonces(o.user, d, c0, nw, k->chain_nonces, (void*)k->stream) != 0) {
+                if (o.fill_nonces(o.user, d, c0, nw, k->chain_nonces.get(), (void*)k->stream) != 0) {
                     sh->failed(PVAC_EINVAL, "ct_mul_chain: fill_nonces callback failed");
                     return;
                 }
-            } else if (!hipchk(launch_fill_random(o.nonce_seed + 97ull * c0 + d, k->chain_nonces, nw, k->stream),
+            } else if (!hipchk(launch_fill_random(o.nonce_seed + 97ull * c0 + d, k->chain_nonces.get(), nw, k->stream),
                                "fill nonces")) {
                 return;
             }
             uint32_t* c_img = nullptr;
             if (use_img && d + 1 < o.depth) {
-                if (kk > S.img_cap && !hipchk(grow_async(S.img, S.img_cap, kk, k->stream), "alloc image flags")) return;
-                if (!hipchk(hipMemsetAsync(S.img, 0, kk * 4, k->stream), "image flags")) return;
-                c_img = S.img;
+                if (!hipchk(S.img.grow_headroom(kk, k->stream), "alloc image flags")) return;
+                if (!hipchk(hipMemsetAsync(S.img.get(), 0, kk * 4, k->stream), "image flags")) return;
+                c_img = S.img.get();
             }
             k->img_in = a_img;
             k->img_out = c_img;
-            k->img_count = k->chain_stats + 2 * PVAC_CHAIN_MAX_DEPTH;
-            if (!rcchk(pvac_hip_ct_mul_exec(k, &plan, &A, &Xv, k->chain_nonces, nullptr, &C, mflags), "exec")) return;
+            k->img_count = k->chain_stats.get() + 2 * PVAC_CHAIN_MAX_DEPTH;
+            if (!rcchk(pvac_hip_ct_mul_exec(k, &plan, &A, &Xv, k->chain_nonces.get(), nullptr, &C, mflags), "exec")) return;
             k->img_out = nullptr;   // the final-step sigma re-run below reads A (img_in), writes records
-            if (!hipchk(launch_chain_stats(A, Xv, C, k->chain_stats + 2 * d, k->stream), "stats")) return;
+            if (!hipchk(launch_chain_stats(A, Xv, C, k->chain_stats.get() + 2 * d, k->stream), "stats")) return;
             if (check) {
                 uint64_t bad = 0;
-                if (!rcchk(pvac_hip_check_mul_gsum(k, &A, &Xv, &C, k->chain_nonces, nullptr, &bad), "gsum check"))
+                if (!rcchk(pvac_hip_check_mul_gsum(k, &A, &Xv, &C, k->chain_nonces.get(), nullptr, &bad), "gsum check"))
                     return;
                 ws->gsum_pairs += kk;
                 ws->gsum_failed += bad;
@@ -2048,9 +1869,9 @@ void chain_worker(pvac_hip_ctx* k, chain_shared* sh, chain_range* rg, bool stage
                 return hipchk(hipMemcpyAsync(to, A.e_cnt, m * 8, hipMemcpyDeviceToDevice, k->stream), "counts");
             };
             if (!remote) return put(dst + c0);
-            if (!hipchk(grow_async(k->chain_out, k->chain_out_cap, m, k->stream), "alloc outputs") || !put(k->chain_out))
+            if (!hipchk(k->chain_out.grow_headroom(m, k->stream), "alloc outputs") || !put(k->chain_out.get()))
                 return false;
-            return hipchk(hipMemcpyPeerAsync(dst + c0, sh->x_dev, k->chain_out, k->device, m * 8, k->stream), "peer copy");
+            return hipchk(hipMemcpyPeerAsync(dst + c0, sh->x_dev, k->chain_out.get(), k->device, m * 8, k->stream), "peer copy");
         };
         if (!out_words(o.digest_n, o.digest_out, 1) || !out_words(o.count_n, o.count_out, 0) ||
             !out_words(o.sumdigest_n, o.sumdigest_out, 2))
@@ -2096,7 +1917,7 @@ int pvac_hip_ct_mul_chain(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac_ch
         if (!batch_ok(&Y) || Y.n != X->n || (Y.n && (!Y.layers || !Y.meta || !Y.w_lo || !Y.w_hi)))
             return fail(c, PVAC_EINVAL, "ct_mul_chain: operand " + std::to_string(d) + " is not a batch of |X| ciphers");
     }
-    if ((o->flags & PVAC_CHAIN_CHECK_GSUM) && !c->powg)
+    if ((o->flags & PVAC_CHAIN_CHECK_GSUM) && !c->powg.get())
         return fail(c, PVAC_EINVAL, "ct_mul_chain: CHECK_GSUM needs pvac_hip_ctx_set_powg");
     if ((o->flags & PVAC_MUL_WITH_SIGMA) && !c->H.ready)
         return fail(c, PVAC_EINVAL, "ct_mul_chain: WITH_SIGMA needs H (pvac_hip_ctx_set_H / gen_H)");
@@ -2119,16 +1940,13 @@ int pvac_hip_ct_mul_chain(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac_ch
     // below are taken over the device's memory, not over what the previous layout's workers left free
     std::vector<int64_t> layout{(int64_t)S, (int64_t)chunk, (int64_t)D};
     layout.insert(layout.end(), devs.begin(), devs.end());
+    device_guard dev(c->device);   // the loops below select the workers' devices
     if (!c->chain_kids.empty() && layout != c->chain_layout) {
         for (pvac_hip_ctx* k : c->chain_kids) {
             hipSetDevice(k->device);
             e = release_chain_worker(k);
-            if (e != hipSuccess) {
-                hipSetDevice(c->device);
-                return hip_fail(c, e, "ct_mul_chain: worker release");
-            }
+            if (e != hipSuccess) return hip_fail(c, e, "ct_mul_chain: worker release");
         }
-        hipSetDevice(c->device);
     }
     c->chain_layout = layout;
     // worker contexts: [range j * S + w] on devs[j]; a layout change rebuilds the ones that differ
@@ -2140,19 +1958,15 @@ int pvac_hip_ct_mul_chain(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac_ch
         // each worker's general-path scratch: its share of half the HBM free now on its device (the
         // other half holds the workers' ping-pong outputs and the caller's data)
         size_t free_b = 0, total_b = 0;
-        if (hipSetDevice(devs[j]) != hipSuccess) {
-            hipSetDevice(c->device);
+        if (hipSetDevice(devs[j]) != hipSuccess)
             return fail(c, PVAC_EDEVICE, "ct_mul_chain: device " + std::to_string(devs[j]));
-        }
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 8ull << 30;
         const uint32_t same = (uint32_t)std::count(devs.begin(), devs.end(), devs[j]);
         const uint64_t cap_words = std::max<uint64_t>((uint64_t)(free_b / 2) / ((uint64_t)S * same) / 4, 1ull << 24);
         if (devs[j] != c->device) {   // peer reads of X / peer writes of the outputs
             const hipError_t pe = hipDeviceEnablePeerAccess(c->device, 0);
-            if (pe != hipSuccess && pe != hipErrorPeerAccessAlreadyEnabled) {
-                hipSetDevice(c->device);
+            if (pe != hipSuccess && pe != hipErrorPeerAccessAlreadyEnabled)
                 return hip_fail(c, pe, "ct_mul_chain: peer access");
-            }
             (void)hipGetLastError();
         }
         for (uint32_t w = 0; w < S; ++w) {
@@ -2165,45 +1979,31 @@ int pvac_hip_ct_mul_chain(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac_ch
             pvac_hip_ctx*& k = c->chain_kids[slot];
             if (!k) {
                 const int rc = pvac_hip_ctx_create(devs[j], &c->prm, &k);
-                if (rc) {
-                    hipSetDevice(c->device);
-                    return fail(c, rc, "ct_mul_chain: worker context");
-                }
-                e = hipMalloc(&k->chain_stats, (2 * PVAC_CHAIN_MAX_DEPTH + 1) * sizeof(unsigned long long));
-                if (e != hipSuccess) {
-                    hipSetDevice(c->device);
-                    return hip_fail(c, e, "ct_mul_chain: worker statistics");
-                }
+                if (rc) return fail(c, rc, "ct_mul_chain: worker context");
             }
+            e = k->chain_stats.grow(2 * PVAC_CHAIN_MAX_DEPTH + 1, 2 * PVAC_CHAIN_MAX_DEPTH + 1);
+            if (e != hipSuccess) return hip_fail(c, e, "ct_mul_chain: worker statistics");
             k->arena_cap_words = cap_words;
             k->prm = c->prm;
             k->spin_us = 200;
             k->img_grid_y = (o->flags & PVAC_CHAIN_IMG_BATCH2) ? 2u : 65535u;
-            if (c->powg && (k->powg_n != c->powg_n || !k->powg)) {
-                hipFree(k->powg);
-                k->powg = nullptr;
-                e = hipMalloc(&k->powg, (size_t)c->powg_n * 16);
-                if (e != hipSuccess) {
-                    hipSetDevice(c->device);
-                    return hip_fail(c, e, "ct_mul_chain: worker powg");
-                }
+            if (c->powg.get() && (k->powg_n != c->powg_n || !k->powg.get())) {
+                k->powg.release();
+                e = k->powg.grow(2 * (size_t)c->powg_n, 2 * (size_t)c->powg_n);
+                if (e != hipSuccess) return hip_fail(c, e, "ct_mul_chain: worker powg");
                 k->powg_n = c->powg_n;
             }
             e = hipSuccess;
-            if (c->powg) e = hipMemcpyPeer(k->powg, k->device, c->powg, c->device, (size_t)c->powg_n * 16);
+            if (c->powg.get()) e = hipMemcpyPeer(k->powg.get(), k->device, c->powg.get(), c->device, (size_t)c->powg_n * 16);
             if (e == hipSuccess && (o->flags & PVAC_MUL_WITH_SIGMA) && (!k->H.ready || k->H_from != c->H_gen)) {
                 e = sigma_tables_clone(k->H, c->H, k->device, c->device, k->stream);
                 k->H_from = c->H_gen;
             }
-            if (e == hipSuccess) e = hipMemsetAsync(k->chain_stats, 0, (2 * PVAC_CHAIN_MAX_DEPTH + 1) * 8, k->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(k->chain_stats.get(), 0, (2 * PVAC_CHAIN_MAX_DEPTH + 1) * 8, k->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(k->stream);
-            if (e != hipSuccess) {
-                hipSetDevice(c->device);
-                return hip_fail(c, e, "ct_mul_chain: worker setup");
-            }
+            if (e != hipSuccess) return hip_fail(c, e, "ct_mul_chain: worker setup");
         }
     }
-    hipSetDevice(c->device);
     std::vector<uint64_t> first(D + 1);
     pvac_hip_chain_partition(X->n, chunk, D, first.data());
     std::vector<chain_range> ranges(D);
@@ -2234,7 +2034,7 @@ int pvac_hip_ct_mul_chain(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac_ch
         e = hipStreamSynchronize(k->stream);
         if (e != hipSuccess && sh.rc == PVAC_OK) sh.failed(PVAC_EDEVICE, std::string("ct_mul_chain: ") + hipGetErrorString(e));
         unsigned long long v[2 * PVAC_CHAIN_MAX_DEPTH + 1];
-        if (hipMemcpy(v, k->chain_stats, sizeof v, hipMemcpyDeviceToHost) == hipSuccess) {
+        if (hipMemcpy(v, k->chain_stats.get(), sizeof v, hipMemcpyDeviceToHost) == hipSuccess) {
             for (uint32_t d = 0; d < o->depth; ++d) {
                 st->edges[d] += v[2 * d];
                 st->products[d] += v[2 * d + 1];
@@ -2246,7 +2046,6 @@ int pvac_hip_ct_mul_chain(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac_ch
         st->chunks += ws[w].chunks;
         st->redo += k->redo_total - redo0[w];
     }
-    hipSetDevice(c->device);
     st->pair_steps = X->n * o->depth;
     st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (sh.rc != PVAC_OK) return fail(c, sh.rc, sh.err);

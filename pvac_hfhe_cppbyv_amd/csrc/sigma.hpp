@@ -4,26 +4,27 @@
 #include <stdint.h>
 
 #include "../../include/pvac_hip.h"
+#include "dev_mem.hpp"
 
 namespace pvhip {
 
-// H stored column-sparse: rows[c * width + k] (u16) for k < counts[c].
+// H stored column-sparse: rows[c * width + k] (u16) for k < counts[c]. The tables own their device
+// arrays, each allocated at its exact size; `T = sigma_tables{}` gives everything back.
 struct sigma_tables {
-    uint16_t* rows = nullptr;
-    uint32_t* counts = nullptr;
+    dev_buf<uint16_t> rows;
+    dev_buf<uint32_t> counts;
     // m_bits == 8192, x_col_wt == 128 and full columns only: the same rows re-encoded for k_sigma's
     // fast column expansion, (r & 31) | (r >> 5) << 7 (bits 5..14 are the image byte offset)
-    uint16_t* rows_fast = nullptr;
+    dev_buf<uint16_t> rows_fast;
     // the same default-geometry columns as 208 byte increments of R = (r >> 5) | (r & 31) << 8
-    // (see k_sigma.hip flip_cols_delta); null when unavailable
-    uint8_t* rows_delta = nullptr;
+    // (see k_sigma.hip flip_cols_delta); empty when unavailable
+    dev_buf<uint8_t> rows_delta;
     uint32_t width = 0;
     uint32_t n_cols = 0;
     bool full = false;   // every column has exactly `width` rows (no padding: k_sigma drops its guards)
     bool ready = false;
 };
 
-void sigma_tables_free(sigma_tables& T);
 // device copy of src for a context on dst_dev (peer copies when the devices differ); synchronous
 hipError_t sigma_tables_clone(sigma_tables& dst, const sigma_tables& src, int dst_dev, int src_dev, hipStream_t st);
 // host SHA-256 over a contiguous buffer
