@@ -33,19 +33,23 @@
 namespace pvhip {
 
 // Census build only (make census -> lib/libpvac_hip_census.so): per-workgroup start / end
-// s_memrealtime (100 MHz) + pairs done; never touches kernel outputs.
+// s_memrealtime (100 MHz) + pairs done, then HW_ID | XCC_ID << 32 of each of its (up to 8) waves;
+// never touches kernel outputs.
 #ifdef PVAC_CENSUS
-__device__ unsigned long long g_census[4096 * 4];
+constexpr int kCensusRow = 3 + 8;
+__device__ unsigned long long g_census[4096 * kCensusRow];
 extern "C" int pvac_hip_diag_census(unsigned long long* host, size_t n) {
     if (n > sizeof(g_census) / 8) n = sizeof(g_census) / 8;
     return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_census), n * 8) == hipSuccess ? 0 : -5;
 }
 #endif
-// Diagnostic build only (make diag -> lib/libpvac_hip_diag.so): wave 0 of every workgroup
-// accumulates s_memtime deltas per phase into a debug array; never touches kernel outputs.
+// Diagnostic build only (make diag -> lib/libpvac_hip_diag.so): lane 0 of every wave of every
+// workgroup accumulates s_memtime deltas per phase into a debug array ([workgroup][wave][phase]);
+// never touches kernel outputs.
 #ifdef PVAC_PHASE_STAMPS
 constexpr int kStampPhases = 18;
-__device__ unsigned long long g_fresh_stamps[4096 * kStampPhases];
+constexpr int kStampWaves = 8;
+__device__ unsigned long long g_fresh_stamps[4096 * kStampWaves * kStampPhases];
 #endif
 
 namespace {
@@ -176,16 +180,21 @@ __device__ __forceinline__ fresh_hdr hdr_decode(uint32_t v, uint64_t q) {
 
 // The pair after q - gridDim.x: q itself when it is a fresh pair (its words v, from LDS), else the
 // next fresh one, whose record every wave loads and the control wave copies into the LDS words
-// (so a barrier must separate this call from the prefetch that reads them).
+// for the prefetch that reads them. That path is rare and taken by the whole workgroup (v and q
+// are workgroup-uniform), so it carries its own barriers: one keeps the control wave from
+// replacing the words before every other wave has read pair q's (a slow wave would decode the new
+// record under the old pair id), one makes the new words visible to the prefetch.
 __device__ __forceinline__ fresh_hdr hdr_next(argp g, uint32_t v, uint64_t q, uint64_t n_pairs, uint32_t* hw) {
     fresh_hdr h{};
     h.pr = kNoPair;
     if (q >= n_pairs) return h;
     if (((uint32_t)__builtin_amdgcn_readlane(v, 15) & 0xFFFFu) != 0) return hdr_decode(v, q);
-    const uint64_t q2 = next_small(g, q + gridDim.x);   // not a fresh pair (rare)
+    __syncthreads();   // not a fresh pair (rare): every wave holds q's words before they are replaced
+    const uint64_t q2 = next_small(g, q + gridDim.x);
     if (q2 == kNoPair) return h;
     const uint32_t v2 = ((const uint32_t*)(g->recs + q2))[threadIdx.x & 15u];
     if ((threadIdx.x >> 6) == (blockDim.x >> 6) - 1 && (threadIdx.x & 63u) < 16) hw[threadIdx.x & 15u] = v2;
+    __syncthreads();
     return hdr_decode(v2, q2);
 }
 static_assert(offsetof(fresh_rec, nb_magic) == 48 && offsetof(fresh_rec, shape) == 56 && offsetof(fresh_rec, nbk) == 60 &&
@@ -363,9 +372,9 @@ __host__ __device__ inline fresh3_layout fresh3_lds(uint32_t ks, uint32_t prod, 
 #ifdef PVAC_PHASE_STAMPS
 #define STAMP3(ph)                                                        \
     do {                                                                  \
-        if (threadIdx.x == 0) {                                           \
+        if ((threadIdx.x & 63u) == 0) {                                   \
             const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-            st3_acc[ph] += now_ - st3_last;                               \
+            st3_acc[(threadIdx.x >> 6) * kStampPhases + (ph)] += now_ - st3_last; \
             st3_last = now_;                                              \
         }                                                                 \
     } while (0)
@@ -421,6 +430,23 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
     uint32_t* misc = (uint32_t*)(lds + Ls.misc);
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // Roles. Bins (P2 / P4), scan segments (P3) and writer sweeps (P6) are dealt by threadIdx: they
+    // fill the waves from 0 up, and the last wave (control) takes none of the writer. Two other ids
+    // are the thread id rotated by whole waves (so every wave-uniform test on them stays
+    // wave-uniform):
+    //   stage_id: edge / layer 0..63 of the next pair belong to the control wave, 64..127 to wave
+    //             0, and so on round. A <= 64-edge pair is loaded and staged by the wave with the
+    //             fewest other duties, while the other waves write.
+    //   prod_id : product 0..63 (and + 512, ...) belong to wave 3, 64..127 to wave 4, and so on
+    //             round, so the partial last product round (the 4th at 40 x 40 edges) is wave 3's.
+    //             Waves w and w + 4 share a SIMD and the hardware serves the older wave first, so
+    //             waves 0..3 finish a round sooner than 4..7: a 4th round on one of them ends P1
+    //             and P5 about when the others' three do (on the control wave it ended them last).
+    //             Wave 3 is the one whose SIMD partner, the control wave, is lightest.
+    constexpr uint32_t kStageRot = 64u, kProdRot = (uint32_t)BS - 192u;
+    static_assert(BS >= 256 && kStageRot % 64u == 0 && kProdRot % 64u == 0, "roles rotate by whole waves");
+    auto stage_id = [] { return opaque((threadIdx.x + kStageRot) % (uint32_t)BS); };
+    auto prod_id = [] { return opaque((threadIdx.x + kProdRot) % (uint32_t)BS); };
     const uint32_t Bm = gq->Bm;
     const uint32_t bdiv = (uint32_t)(0x100000000ull / Bm) + 1u;   // s / Bm = mulhi(s, bdiv) for s < 2^16
     const uint32_t dummy = gq->ks_max;   // a slot whose two cell words are never set (tk_words > 2 ks_max + 1)
@@ -429,6 +455,10 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
     // the bucket has more than 3 others; then m0 = CSR start into `members`, rec1 = their number.
     // Slot k of a thread has rank tid + k*BS in mate-count order (descending), so lane 0 of a wave
     // holds that wave's largest count for row k (cmax, wave-uniform).
+    // cmax[k] (wave-uniform) is the kind of this wave's bins in row k. Bins are laid out by kind
+    // (big, size-3, a size-2 bucket with a single, three singles), so most waves hold one kind and
+    // P2 / P4 run a straight-line body for the three common ones.
+    enum : uint32_t { kBinsNone = 0, kBinsMixed = 1, kBinsSingles = 2, kBinsPair = 3, kBinsTriple = 4 };
     uint32_t rec0[KR], rec1[KR], cmax[KR];
 #pragma unroll
     for (int k = 0; k < KR; ++k) {
@@ -447,9 +477,11 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
     __syncthreads();
 
 #ifdef PVAC_PHASE_STAMPS
-    // diagnostic build: phase times of thread 0 accumulated in LDS (registers would cost occupancy)
-    __shared__ unsigned long long st3_acc[kStampPhases];
-    if (threadIdx.x < kStampPhases) st3_acc[threadIdx.x] = 0;
+    // diagnostic build: phase times of every wave's lane 0 accumulated in LDS (registers would cost
+    // occupancy)
+    static_assert(NW <= kStampWaves && NW * kStampPhases <= BS, "stamp rows");
+    __shared__ unsigned long long st3_acc[NW * kStampPhases];
+    if (threadIdx.x < NW * kStampPhases) st3_acc[threadIdx.x] = 0;
     unsigned long long st3_last = __builtin_amdgcn_s_memtime();
 #endif
 #ifdef PVAC_CENSUS
@@ -469,7 +501,10 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
         }
     }
     __syncthreads();
-    stage_pair(prefetch_pair(gq, cur, misc + F3_HDR), cur, Bm, a_w, a_inf, b_w, b_inf, pm, misc);
+    {
+        const uint32_t rid = stage_id();
+        stage_pair(prefetch_pair(gq, cur, misc + F3_HDR, rid), cur, Bm, a_w, a_inf, b_w, b_inf, pm, misc, rid);
+    }
     __syncthreads();
 
     while (cur.pr != kNoPair) {
@@ -495,8 +530,10 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
             if (wave == NW - 1 && lane < 16) misc[F3_HDR + lane] = hv;
             __syncthreads();
             const fresh_hdr nx = hdr_next(gq, misc[F3_HDR + (lane & 15)], qn, n_pairs, misc + F3_HDR);
-            __syncthreads();   // (hdr_next may have replaced the LDS words)
-            stage_pair(prefetch_pair(gq, nx, misc + F3_HDR), nx, Bm, a_w, a_inf, b_w, b_inf, pm, misc);
+            {
+                const uint32_t rid = stage_id();
+                stage_pair(prefetch_pair(gq, nx, misc + F3_HDR, rid), nx, Bm, a_w, a_inf, b_w, b_inf, pm, misc, rid);
+            }
             __syncthreads();
             cur = nx;
             continue;
@@ -617,7 +654,16 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
                 const uint32_t q = tid + (uint32_t)k * BS;
                 rec0[k] = q < nbins ? drec[2u * q] : dummy | (dummy << 16);
                 rec1[k] = q < nbins ? drec[2u * q + 1u] : dummy;
-                cmax[k] = __builtin_amdgcn_readfirstlane(q < nbins ? 1u : 0u);   // row has bins in this wave
+                // lanes past the last bin hold dummy slots with no flags: they run any body unharmed
+                const uint32_t fl = q < nbins ? rec1[k] >> 16 : 0u;
+                const bool singles = __builtin_amdgcn_ballot_w64(fl != 0u) == 0;
+                const bool pairs = __builtin_amdgcn_ballot_w64(q < nbins && fl != 1u) == 0;
+                const bool triples = __builtin_amdgcn_ballot_w64(q < nbins && fl != 7u) == 0;
+                cmax[k] = __builtin_amdgcn_readfirstlane(q < nbins ? 1u : 0u) == 0u ? kBinsNone   // lane 0: the first bin
+                          : singles                                               ? kBinsSingles
+                          : pairs                                                 ? kBinsPair
+                          : triples                                               ? kBinsTriple
+                                                                                  : kBinsMixed;
             }
             nbk_c = nbk;
             __syncthreads();
@@ -638,7 +684,7 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
 #pragma unroll
         for (int u = 0; u < U; ++u) prod[u] = ~0u;
         {
-            const uint32_t tid = opaque(threadIdx.x);
+            const uint32_t tid = prod_id();
             for (uint32_t t0 = tid; t0 < n; t0 += U * BS) {
                 uint32_t sum[U], ij[U];
 #pragma unroll
@@ -659,12 +705,10 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
             }
         }
         STAMP3_SYNC(1);
-        if (wave == NW - 1 && lane < 16) misc[F3_HDR + lane] = hv;   // its load has had P1 to land
         __syncthreads();
         STAMP3(2);
         gq = launder(gq);
         __builtin_amdgcn_s_setprio(1);
-        const fresh_hdr nxt = hdr_next(gq, misc[F3_HDR + (lane & 15)], qn, n_pairs, misc + F3_HDR);
 
         M3(2);
         // ---- P2: per bin (up to 3 slots whose buckets lie wholly in the bin): key time and emit
@@ -681,7 +725,7 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
             for (int k = 0; k < KR; ++k) {
                 ordA[k] = kT16 | (kT16 << 16);
                 ordB[k] = kT16;
-                if (cmax[k] == 0u) continue;   // wave-uniform: no bin in this row
+                if (cmax[k] == kBinsNone) continue;   // wave-uniform: no bin in this row
                 const uint32_t fl = rec1[k] >> 16;
                 const bool big = (fl & 8u) != 0;
                 const uint32_t m0 = big ? dummy : rec0[k] & 0xFFFFu, m1 = big ? dummy : rec0[k] >> 16;
@@ -691,6 +735,33 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
                 cells(tk64[m1], t1, e1);
                 cells(tk64[m2], t2, e2);
                 const uint32_t p0 = __popc(e0), p1 = __popc(e1), p2 = __popc(e2);
+                if (cmax[k] == kBinsSingles) {   // three buckets of one slot: t_bkt = key time, rank 0
+                    if (t0 != kT16) tk16[2u * t0 + 1u] = (uint16_t)p0;
+                    if (t1 != kT16) tk16[2u * t1 + 1u] = (uint16_t)p1;
+                    if (t2 != kT16) tk16[2u * t2 + 1u] = (uint16_t)p2;
+                    ordA[k] = t0 | (t1 << 16);
+                    ordB[k] = t2 | (e0 << 25) | (e1 << 27) | (e2 << 29);
+                    continue;
+                }
+                if (cmax[k] == kBinsPair) {   // slots 0 and 1 share a bucket, slot 2 (if any) has its own
+                    const uint32_t tb = min(t0, t1);
+                    if (tb != kT16) tk16[2u * tb + 1u] = (uint16_t)(p0 + p1);
+                    if (t2 != kT16) tk16[2u * t2 + 1u] = (uint16_t)p2;
+                    const uint32_t wi0 = t1 > t0 ? p1 : 0u, wi1 = t0 > t1 ? p0 : 0u;
+                    ordA[k] = tb | (tb << 16);
+                    ordB[k] = t2 | (wi0 << 16) | (wi1 << 19) | (e0 << 25) | (e1 << 27) | (e2 << 29);
+                    continue;
+                }
+                if (cmax[k] == kBinsTriple) {   // one bucket of three slots
+                    const uint32_t tb = min(t0, min(t1, t2));
+                    if (tb != kT16) tk16[2u * tb + 1u] = (uint16_t)(p0 + p1 + p2);
+                    const uint32_t wi0 = (t1 > t0 ? p1 : 0u) + (t2 > t0 ? p2 : 0u);
+                    const uint32_t wi1 = (t0 > t1 ? p0 : 0u) + (t2 > t1 ? p2 : 0u);
+                    const uint32_t wi2 = (t0 > t2 ? p0 : 0u) + (t1 > t2 ? p1 : 0u);
+                    ordA[k] = tb | (tb << 16);
+                    ordB[k] = tb | (wi0 << 16) | (wi1 << 19) | (wi2 << 22) | (e0 << 25) | (e1 << 27) | (e2 << 29);
+                    continue;
+                }
                 const bool f01 = fl & 1u, f02 = fl & 2u, f12 = fl & 4u;
                 // times are distinct when present; an absent slot has no edges (p = 0)
                 const uint32_t wi0 = (f01 && t1 > t0 ? p1 : 0u) + (f02 && t2 > t0 ? p2 : 0u);
@@ -788,9 +859,15 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
             __builtin_amdgcn_s_setprio(1);
         }
         STAMP3_SYNC(5);
+        // The next pair's header words go to LDS only here: the record comes from HBM under the
+        // kernel's store traffic, and the control wave's wait for it stood before P1's barrier,
+        // which every wave shares. Nothing before the prefetch at the end of P4 needs the next
+        // pair, so the load now has P1 to P3 to land (-1.5%, A/B).
+        if (wave == NW - 1 && lane < 16) misc[F3_HDR + lane] = hv;
         __syncthreads();
         STAMP3(6);
         gq = launder(gq);
+        const fresh_hdr nxt = hdr_next(gq, misc[F3_HDR + (lane & 15)], qn, n_pairs, misc + F3_HDR);
 
         M3(4);
         // ---- P4: segment offsets (suffix over the segment totals, lane g holds segment g's),
@@ -838,11 +915,14 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
             };
 #pragma unroll
             for (int k = 0; k < KR; ++k) {
-                if (cmax[k] == 0u) continue;   // wave-uniform
+                if (cmax[k] == kBinsNone) continue;   // wave-uniform
                 const uint32_t fl = rec1[k] >> 16;
                 const bool big = (fl & 8u) != 0;
                 const uint32_t tb0 = ordA[k] & kT16, tb1 = ordA[k] >> 16, tb2 = ordB[k] & kT16;
-                const uint32_t o0 = offset(tb0), o1 = offset(tb1), o2 = offset(tb2);
+                const uint32_t o0 = offset(tb0);
+                const bool one01 = cmax[k] == kBinsPair || cmax[k] == kBinsTriple;   // (wave-uniform) one bucket
+                const uint32_t o1 = one01 ? o0 : offset(tb1);
+                const uint32_t o2 = cmax[k] == kBinsTriple ? o0 : offset(tb2);
                 if (!big) {
                     emit(rec0[k] & 0xFFFFu, (ordB[k] >> 25) & 3u, o0 + ((ordB[k] >> 16) & 7u));
                     emit(rec0[k] >> 16, (ordB[k] >> 27) & 3u, o1 + ((ordB[k] >> 19) & 7u));
@@ -902,7 +982,7 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
             misc[F3_BMASK] = 0;
         }
         // next pair's raw inputs: in flight through P5 and the writer, staged after them
-        const fresh_pref pf = prefetch_pair(gq, nxt, misc + F3_HDR, opaque(threadIdx.x));
+        const fresh_pref pf = prefetch_pair(gq, nxt, misc + F3_HDR, stage_id());
         STAMP3_SYNC(7);
         __syncthreads();
         STAMP3(8);
@@ -912,7 +992,7 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
         M3(5);
         // ---- P5: products into the limb accumulators of their emit positions
         {
-            const uint32_t tid = opaque(threadIdx.x);
+            const uint32_t tid = prod_id();
             auto accumulate = [&](const ulonglong2& x, const ulonglong2& y, uint32_t p) {
                 uint64_t x0, x1, l0, l1, l2;
                 fp_mul_fold1(fp{x.x, x.y}, fp{y.x, y.y}, x0, x1);
@@ -958,7 +1038,7 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
         //      writer's stores would have to wait for those too: vmcnt counts both in order), then
         //      the coalesced writer over emit positions (not the control wave: its vector-memory
         //      queue stays free of stores), then clear the cell words
-        stage_pair(pf, nxt, Bm, a_w, a_inf, b_w, b_inf, pm, misc, opaque(threadIdx.x));
+        stage_pair(pf, nxt, Bm, a_w, a_inf, b_w, b_inf, pm, misc, stage_id());
         {
             const uint32_t tid = opaque(threadIdx.x);
             uint64_t* cm = gq->C.meta + ceo;
@@ -1019,18 +1099,24 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
 #endif
     }
 #ifdef PVAC_CENSUS
-    if (threadIdx.x == 0 && blockIdx.x < 4096) {
-        unsigned hw;
+    if (lane == 0 && blockIdx.x < 4096) {
+        static_assert(NW <= kCensusRow - 3, "census row");
+        unsigned hw, xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        g_census[4 * blockIdx.x] = cen_t0;
-        g_census[4 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
-        g_census[4 * blockIdx.x + 2] = cen_pairs;
-        g_census[4 * blockIdx.x + 3] = hw;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        unsigned long long* row = g_census + (size_t)kCensusRow * blockIdx.x;
+        if (wave == 0) {
+            row[0] = cen_t0;
+            row[1] = __builtin_amdgcn_s_memrealtime();
+            row[2] = cen_pairs;
+        }
+        row[3 + wave] = hw | ((unsigned long long)xcc << 32);
     }
 #endif
 #ifdef PVAC_PHASE_STAMPS
-    if (threadIdx.x == 0 && blockIdx.x < 4096)
-        for (int p = 0; p < kStampPhases; ++p) g_fresh_stamps[blockIdx.x * kStampPhases + p] = st3_acc[p];
+    __syncthreads();
+    if (threadIdx.x < NW * kStampPhases && blockIdx.x < 4096)
+        g_fresh_stamps[(size_t)blockIdx.x * kStampWaves * kStampPhases + threadIdx.x] = st3_acc[threadIdx.x];
 #endif
 }
 
