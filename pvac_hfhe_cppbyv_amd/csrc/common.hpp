@@ -362,8 +362,21 @@ hipError_t launch_ct_mul_large(const mul_large_args& a, hipStream_t st);
 // listed pair (sum of their |A.E|); launches of at most y_cap pairs each (65535: the grid-y limit)
 hipError_t launch_image_to_records(const pvac_ct_batch& A, uint32_t* img, const uint64_t* pairs, uint32_t n_pairs,
                                    uint64_t* tmp, uint32_t Bm, uint32_t y_cap, hipStream_t st);
-// LDS of k_large_products_direct for B and nbl staged B layers (the direct mode needs it <= 160 KB)
-uint32_t large_direct_lds_bytes(uint32_t Bm, uint32_t nbl);
+__host__ __device__ inline uint32_t al16(uint32_t x) { return (x + 15u) & ~15u; }
+// matrix-core dense mode (k_mul_large.hip): a task's sparse side is staged as prec | pinf
+constexpr int kMxKS = 10;                          // k-steps held in registers: 2 sparse edges each
+constexpr uint32_t kMxMaxSparse = 2u * kMxKS;      // sparse sides up to this size take the MFMA path
+constexpr uint32_t kMxSparseBytes = 64u * kMxMaxSparse;
+constexpr uint32_t kIblkBjtBytes = 4u * 64u;       // k_large_products_la: B edge table of iblk pairs
+// LDS of k_large_products_direct for B and nbl staged B layers (the direct mode needs it <= 160 KB;
+// the layout is described at the kernel)
+__host__ __device__ inline uint32_t dir_lds_base(uint32_t Bm) {   // the digit table, reused by the writer
+    // okey [8 B] u16 | obase, oidx, oexc [256] u32 | omk [256] 16 B | part
+    return al16(max(32u * Bm, 16u * Bm + 28u * 256u + 64u));
+}
+__host__ __device__ inline uint32_t dir_lds_bytes(uint32_t Bm, uint32_t nbl) {
+    return dir_lds_base(Bm) + nbl * kMxSparseBytes + kIblkBjtBytes + nbl * 32u * Bm;
+}
 // measured integer-ALU ceilings (k_ubench.hip)
 hipError_t run_alu_probe(int kind, int num_cus, hipStream_t st, double* per_s);
 hipError_t run_issue_probe(int op, int wps, int num_cus, hipStream_t st, double* per_s, double* clock_hz);

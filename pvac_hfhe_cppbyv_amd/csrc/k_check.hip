@@ -48,8 +48,6 @@ struct check_lds {   // byte offsets into dynamic LDS
     uint32_t powg, accA, accB, accC, cntC, cand, found, total;
 };
 
-__host__ __device__ inline uint32_t al16(uint32_t x) { return (x + 15u) & ~15u; }
-
 __host__ __device__ inline check_lds check_layout(uint32_t Bm, uint32_t la, uint32_t lb, uint32_t lc, uint32_t lp) {
     check_lds L;
     uint32_t o = 0;

@@ -283,7 +283,6 @@ constexpr uint32_t kChunk = 128;         // sparse-side edges staged per round (
 // one product per sparse edge goes into each lane's P and M column sets between col26_norm calls
 static_assert(kChunk <= kCol26MaxProducts, "col26 columns overflow: normalise more often");
 
-__host__ __device__ inline uint32_t al16(uint32_t x) { return (x + 15u) & ~15u; }
 // dense mode: dl4[2][2B] (limbs 0-3, 16 B) | dx[2][2B] (limb 4, first-insert share) | sl4[kChunk]
 //             (16 B) | sl1[kChunk] | sinf[kChunk] | sid[kChunk] | dup. Per channel the B dense slots
 //             are stored twice (x and x + B), so lane r finds slot (r - sidx) mod B at r + B - sidx:
@@ -309,8 +308,6 @@ __host__ __device__ inline uint32_t prod_lds_bytes(uint32_t Bm) {
 typedef int mx_v4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u2v __attribute__((ext_vector_type(2)));
 typedef int mx_v16 __attribute__((ext_vector_type(16)));
-constexpr int kMxKS = 10;                          // k-steps held in registers: 2 sparse edges each
-constexpr uint32_t kMxMaxSparse = 2u * kMxKS;      // sparse sides up to this size take the MFMA path
 static_assert(kMxMaxSparse == kIblkMaxSparse, "iblk pairs need every B layer on the matrix cores");
 constexpr uint64_t kDigC = 0x8080808080808080ull;  // 128 in every byte
 #ifdef PVAC_ASM_MARKS   // ISA census builds only (tools/asm_phases.py)
@@ -407,8 +404,6 @@ __host__ __device__ inline uint32_t mx_lds_bytes(uint32_t Bm) { return al16(80u 
 // the B layers' staging at cnt_lds_bytes (6 workgroups per CU where mx_lds_bytes allowed 4)
 constexpr uint32_t kCntTtOff = 32u;
 __host__ __device__ inline uint32_t cnt_lds_bytes(uint32_t Bm) { return al16((kCntTtOff + 16u) * Bm + 8u); }
-constexpr uint32_t kMxSparseBytes = 64u * kMxMaxSparse;
-constexpr uint32_t kIblkBjtBytes = 4u * 64u;       // k_large_products_la: B edge table of iblk pairs
 
 // the dense side of a task into dig / tt. Every thread calls it; barriers inside; false
 // (workgroup-uniform) when the layer holds duplicate (idx, ch) edges
@@ -1418,14 +1413,8 @@ __global__ __launch_bounds__(BS, kLaMinBlocks) void k_large_products_la(mul_larg
 // the host's redo.
 //
 // LDS: dig1 [2][B] uint4 (one copy per channel: slot (r - idx) mod B with a wrap, 32 B per index) |
-// per B layer: prec | pinf (kMxSparseBytes) | bjt [64] | stg [neB][B][2] (16 B per cell)
-__host__ __device__ inline uint32_t dir_lds_base(uint32_t Bm) {   // the digit table, reused by the writer
-    // okey [8 B] u16 | obase, oidx, oexc [256] u32 | omk [256] 16 B | part
-    return al16(max(32u * Bm, 16u * Bm + 28u * 256u + 64u));
-}
-__host__ __device__ inline uint32_t dir_lds_bytes(uint32_t Bm, uint32_t nbl) {
-    return dir_lds_base(Bm) + nbl * kMxSparseBytes + kIblkBjtBytes + nbl * 32u * Bm;
-}
+// per B layer: prec | pinf (kMxSparseBytes) | bjt [64] | stg [neB][B][2] (16 B per cell): dir_lds_bytes
+// (common.hpp; the host sizes the direct mode by it)
 
 // the dense side (an A layer) as digits, one copy per channel (k_large_count_la checked for
 // duplicate cells). Barriers inside; every thread calls it.
@@ -2387,8 +2376,6 @@ hipError_t launch_grp_build(fastmod64 nbm, uint32_t Bm, uint64_t S, uint32_t hbi
                        (const uint32_t*)tmp_head);
     return hipGetLastError();
 }
-
-uint32_t large_direct_lds_bytes(uint32_t Bm, uint32_t nbl) { return dir_lds_bytes(Bm, nbl); }
 
 // ---------------------------------------------------------------- dense chain images -> records
 // (k_large_products_direct's image writer; see mul_large_args::A_img) Listed pair y (pairs[y], its

@@ -12,16 +12,15 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
-#include <tuple>
 #include <new>
 #include <mutex>
 #include <string>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
 #include "common.hpp"
 #include "dev_mem.hpp"
+#include "large_plan.hpp"
 #include "sigma.hpp"
 #include "sha256.hpp"
 
@@ -48,6 +47,27 @@ struct chain_set {
         for (dev_stream_buf<uint64_t>* b : {&l_off, &l_cnt, &e_off, &e_cnt, &meta, &w_lo, &w_hi, &sigma}) b->release(st);
         layers.release(st);
         img.release(st);
+    }
+    // the four per-cipher arrays for n ciphers
+    hipError_t grow_index(size_t n, hipStream_t st) {
+        hipError_t e = hipSuccess;
+        for (dev_stream_buf<uint64_t>* b : {&l_off, &l_cnt, &e_off, &e_cnt})
+            if (e == hipSuccess) e = b->grow_headroom(n, st);
+        return e;
+    }
+    // the batch of n ciphers over the buffers as they are now (no sigma)
+    pvac_ct_batch view(uint64_t n) const {
+        pvac_ct_batch v{};
+        v.n = n;
+        v.l_off = l_off.get();
+        v.l_cnt = l_cnt.get();
+        v.layers = layers.get();
+        v.e_off = e_off.get();
+        v.e_cnt = e_cnt.get();
+        v.meta = meta.get();
+        v.w_lo = w_lo.get();
+        v.w_hi = w_hi.get();
+        return v;
     }
 };
 
@@ -89,16 +109,15 @@ struct pvac_hip_ctx {
     dev_buf<uint64_t> prf_core;
     dev_buf<uint8_t> enc_arena;
     // general ct_mul path: host descriptors of the last plan, device copies, scratch arena
-    std::vector<large_desc> large_host;
-    std::vector<large_desc> large_exec;
+    std::vector<large_desc> large_host;   // the latest plan's pairs, in pair order
+    sub_batch sub;                        // the sub-batch being launched (run_large)
     uint32_t plan_stamp = 0;
     uint64_t last_mul_pairs = 0;       // pairs of the last ct_mul_exec (pair_status is valid for these)
     uint64_t redo_total = 0;           // pairs re-run by redo_fresh_pairs since the context was created
     uint64_t path_total[4] = {};       // pair launches: fresh kernel, general path, its iblk order, direct mode
     double noise_bits = 120.0, noise_t2 = 0.55, noise_slope = 16.0;   // Params noise fields (enc plan_noise)
     dev_buf<large_desc> desc_dev;
-    dev_buf<uint32_t> sel_dev;         // products: descriptor order per sub-batch (A-layer-major class first)
-    std::vector<uint32_t> sel_host;
+    dev_buf<uint32_t> sel_dev;         // products: descriptor order per sub-batch (sub_batch::sel)
     dev_buf<uint32_t> arena;           // in 32-bit words
     // static bucket-group tables of the last plan (one per distinct bucket count) + build scratch
     dev_buf<uint32_t> grp, grp_tmp;
@@ -120,12 +139,6 @@ struct pvac_hip_ctx {
     std::vector<hipEvent_t> ev_pool;   // timer events returned by flush_timers, reused (no create per launch)
     // general-path scratch cap in words (0 = half the free HBM): chain workers share the device
     uint64_t arena_cap_words = 0;
-    bool large_no_direct = false;   // the redo run: every pair on the full (per-key sums) layout
-    // chain steps: per-pair dense-image flags of A (read; cleared where A is turned back into records)
-    // and of C (written) for the next exec (mul_large_args::A_img / C_img); null outside the chain
-    uint32_t* img_in = nullptr;
-    uint32_t* img_out = nullptr;
-    unsigned long long* img_count = nullptr;   // chain: pair-steps written as images (chain_stats' last word)
     dev_buf<uint64_t> img_tmp;         // image -> records: 3 words per edge of the pairs converted
     dev_buf<uint64_t> img_pairs;       // [2 n]: pair ids, then their offsets in img_tmp
     uint32_t img_grid_y = 65535;       // pairs per image -> records launch (PVAC_CHAIN_IMG_BATCH2: 2)
@@ -155,15 +168,6 @@ int hip_fail(pvac_hip_ctx* c, hipError_t e, const char* where) {
     if (e == hipSuccess) return PVAC_OK;
     std::string m = std::string(where) + ": " + hipGetErrorString(e);
     return fail(c, e == hipErrorOutOfMemory ? PVAC_ENOMEM : PVAC_EDEVICE, m);
-}
-
-// libstdc++ bucket count chosen by std::unordered_map::reserve(n) on an empty map: the
-// container rehashes to _M_next_bkt(max(1, ceil(n / max_load_factor))) with max load 1.0.
-// Asking the policy object directly gives the identical value without allocating.
-uint64_t bucket_count_after_reserve(uint64_t n) {
-    std::__detail::_Prime_rehash_policy pol(1.0f);
-    const uint64_t want = std::max<uint64_t>(1, (uint64_t)pol._M_bkt_for_elements(n));
-    return pol._M_next_bkt(want);
 }
 
 struct scoped_timer {
@@ -267,125 +271,6 @@ int ensure_pairs(pvac_hip_ctx* c, size_t n) {
 
 bool batch_ok(const pvac_ct_batch* X) {
     return X && (X->n == 0 || (X->l_off && X->l_cnt && X->e_off && X->e_cnt));
-}
-
-uint32_t ceil_log2(uint64_t x) {
-    uint32_t b = 0;
-    while ((1ull << b) < x) ++b;
-    return b;
-}
-
-// Scratch layout of one general-path pair (k_mul_large.hip), offsets relative to 0; the
-// executor rebases them into the arena. 64-bit arrays on even words, 16-byte arrays on
-// multiples of four.
-int build_large_desc(large_desc& d, uint64_t pair, uint64_t LA, uint64_t LB, uint64_t nA, uint64_t nB, uint32_t Bm,
-                     std::string& why, bool static_grp = false, bool allow_direct = false) {
-    d = large_desc{};
-    d.pair = pair;
-    d.n = nA * nB;
-    d.S = LA * LB * Bm;
-    d.Lc = LA + LB + LA * LB;
-    if (LA > 0xFFFFFFFFull || LB > 0xFFFFFFFFull || nA > 0xFFFFFFFFull || nB > 0xFFFFFFFFull ||
-        (nA && d.n / nA != nB) || d.n >= (1ull << 32)) {
-        why = "ct_mul: |A.E||B.E| >= 2^32 products in one pair";
-        return PVAC_ENOSYS;
-    }
-    if (d.Lc > kLargeLayersMax) {
-        why = "ct_mul: more than " + std::to_string(kLargeLayersMax) + " layers before compaction in one pair";
-        return PVAC_ENOSYS;
-    }
-    if (d.S >= (1ull << 31)) {
-        why = "ct_mul: key space |A.L||B.L|B >= 2^31";
-        return PVAC_ENOSYS;
-    }
-    d.LA = (uint32_t)LA; d.LB = (uint32_t)LB; d.nA = (uint32_t)nA; d.nB = (uint32_t)nB;
-    d.nblk = (d.n + 15) / 16;
-    const uint64_t keys = std::min(d.n, d.S);
-    d.capE = 2 * keys;
-    d.nbm = make_fastmod64(bucket_count_after_reserve(d.n));
-    d.hbits = std::max<uint32_t>(1, ceil_log2(2 * std::max<uint64_t>(keys, 1)));
-    d.g_head = d.g_next = kNoGrp;
-    // per-A-edge emit order (k_mul_large.hip): static groups and the A-layer-major products kernel
-    d.iblk = static_grp && LB <= kLaMaxLB && nA >= 1 && nB >= 1 && nB <= kIblkMaxNB ? 1u : 0u;
-    // (direct A ids and writer lists pack an A edge with its dense cell: A edges < 2^21, 2 B <= 2^11)
-    // (and k_large_products_direct's LDS: the digit table, LB staged B layers and their sums)
-    d.direct = d.iblk && allow_direct && nA < (1ull << 21) && Bm <= 1024u &&
-                       large_direct_lds_bytes(Bm, (uint32_t)LB) <= 160u * 1024u
-                   ? 1u
-                   : 0u;
-    d.nb_m = nB ? (1ull << 32) / nB : 0;
-    uint64_t o = 0;
-    auto even = [&]() { o = (o + 1) & ~1ull; };
-    auto quad = [&]() { o = (o + 3) & ~3ull; };
-    if (d.direct) {
-        // no per-key scratch: cnt | used, the edge lists, per-A-edge counts and masks
-        quad();
-        d.o_zero = d.o_cnt = o;
-        o += kCntWords;
-        d.o_hkey = d.o_hhead = d.o_bmask = o;
-        d.o_bcnt = d.o_used = o;
-        o += d.Lc;
-        d.zero_words = o - d.o_zero;
-        d.o_tkey = o;
-        d.o_lstA = o; o += 2 * LA + nA;
-        d.o_lstB = o; o += 2 * LB + nB;
-        d.o_neA = o; o += LA;
-        d.o_neB = o; o += LB;
-        d.o_defer = d.o_info = d.o_sums = d.o_nxt = d.o_tb = d.o_within = d.o_etot = d.o_cpos = d.o_order = d.o_hpos = o;
-        const uint64_t ngrp = (nA + 31) / 32;
-        quad();
-        d.o_icnt = o; o += 8 * ngrp;   // count bytes
-        d.o_iwo = o; o += ngrp;
-        d.o_wle = o; o += nA;
-        d.o_wln = o; o += LA;
-        quad();
-        d.o_imask = o; o += 4 * nA;
-        quad();
-        d.words = o;
-        return PVAC_OK;
-    }
-    const uint64_t hcap = static_grp ? 0 : 1ull << d.hbits;   // static groups: no bucket table / chains
-    quad();
-    d.o_zero = o;
-    d.o_cnt = o; o += kCntWords;
-    d.o_hkey = o; o += 2 * hcap;
-    d.o_hhead = o; o += hcap;
-    even();
-    d.o_bmask = o; o += 2 * d.nblk;
-    d.o_bcnt = o;
-    d.o_used = o; o += d.Lc;
-    d.zero_words = o - d.o_zero;
-    d.o_tkey = o; o += d.S;
-    d.o_lstA = o; o += 2 * LA + nA;
-    d.o_lstB = o; o += 2 * LB + nB;
-    d.o_neA = o; o += LA;
-    d.o_neB = o; o += LB;
-    d.o_defer = o; o += LA * LB <= kLaMaxLB * LA ? LA * LB : 0;   // A-layer-major pairs only
-    d.o_info = o; o += d.S;
-    quad();
-    d.o_sums = o; o += 8 * d.S;
-    d.o_nxt = o; o += static_grp ? 0 : d.S;
-    d.o_tb = o; o += d.S;
-    d.o_within = o; o += d.S;
-    d.o_etot = o; o += d.S;
-    d.o_cpos = o; o += d.S;
-    d.o_order = o; o += d.capE;
-    d.o_hpos = o; o += d.capE;
-    d.o_icnt = o; o += d.iblk ? nA : 0;
-    quad();
-    d.o_imask = o; o += d.iblk ? 4 * nA : 0;
-    quad();
-    d.o_wle = d.o_wln = d.o_iwo = o;
-    d.words = o;
-    return PVAC_OK;
-}
-
-void rebase_desc(large_desc& d, uint64_t base) {
-    uint64_t* f[] = {&d.o_zero, &d.o_cnt, &d.o_hkey, &d.o_hhead, &d.o_bmask, &d.o_bcnt, &d.o_used, &d.o_tkey,
-                     &d.o_lstA, &d.o_lstB, &d.o_neA, &d.o_neB, &d.o_defer, &d.o_info, &d.o_sums, &d.o_nxt, &d.o_tb,
-                     &d.o_within, &d.o_etot, &d.o_cpos, &d.o_order, &d.o_hpos, &d.o_icnt, &d.o_imask,
-                     &d.o_wle, &d.o_wln, &d.o_iwo};
-    for (uint64_t* p : f) *p += base;
 }
 
 }  // namespace
@@ -566,48 +451,19 @@ int pvac_hip_fp_binop(pvac_hip_ctx* c, int op, const uint64_t* a_lo, const uint6
 // ---------------------------------------------------------------- ct_mul
 namespace {
 
-// Whether two key slots of [0, S) share a libstdc++ bucket among nb buckets (std::hash<u64> times the
-// reference's 0x9E3779B97F4A7C15, arithmetic.hpp:72-77). A pair whose slots can share a bucket is not
-// taken in the direct mode (its emit order then needs bucket leaders across A layers): chain step 2
-// (|A.L| = 8, bucket counts near 49 K) has hundreds of such buckets, deeper steps none (the structured
-// keys (lp << 32) | r spread perfectly there). Memoised per (nb, S, B): chunks of one step repeat them,
-// and the slot -> key map depends on B (two contexts with different B can meet the same (nb, S)).
-bool slots_share_bucket(uint64_t nb, uint64_t S, uint32_t Bm) {
-    static std::mutex mu;
-    static std::map<std::tuple<uint64_t, uint64_t, uint32_t>, bool> memo;
-    {
-        std::lock_guard<std::mutex> g(mu);
-        auto it = memo.find({nb, S, Bm});
-        if (it != memo.end()) return it->second;
-    }
-    bool shared = false;
-    if (S > nb) {
-        shared = true;
-    } else {
-        std::vector<uint64_t> seen((nb + 63) / 64, 0);
-        for (uint64_t s = 0; s < S && !shared; ++s) {
-            const uint64_t key = ((s / Bm) << 32) | (s % Bm);
-            const uint64_t b = (key * kGolden) % nb;
-            const uint64_t m = 1ull << (b & 63);
-            shared = (seen[b >> 6] & m) != 0;
-            seen[b >> 6] |= m;
-        }
-    }
-    std::lock_guard<std::mutex> g(mu);
-    memo[{nb, S, Bm}] = shared;
-    return shared;
-}
-
 // Pairs whose bucket count is at least twice their key-slot space (dense chain steps: reserve(|A.E||B.E|)
 // buckets for |A.L||B.L|B slots) share their bucket groups with every pair of the same bucket count:
 // the group of a slot depends only on (slot, B, bucket count). One static table per distinct bucket
 // count replaces the per-pair bucket table + chains (k_large_link) and its zeroing; rank walks the
 // static group and keeps the slots present in the pair (almost every slot is alone in its bucket).
-int plan_static_groups(pvac_hip_ctx* c) {
+// Builds the tables of `set` into the context's one buffer (c->grp: they replace those of any other
+// set) and rebuilds the descriptors of its pairs that use them; allow_direct = false keeps every
+// pair on the full layout (per-key sums: the redo run, the canonical order).
+int assign_static_groups(pvac_hip_ctx* c, std::vector<large_desc>& set, bool allow_direct) {
     constexpr size_t kMaxCfg = 64;
     constexpr uint64_t kMaxWords = 1ull << 28;   // <= 1 GiB of tables
     std::map<uint64_t, uint64_t> cfg;             // bucket count -> max S
-    for (const large_desc& d : c->large_host)
+    for (const large_desc& d : set)
         if (d.nbm.d >= 2 * d.S && d.S) {
             uint64_t& m = cfg[d.nbm.d];
             m = std::max(m, d.S);
@@ -637,19 +493,44 @@ int plan_static_groups(pvac_hip_ctx* c) {
         off[kv.first] = o;
         o += 2 * Sm;
     }
-    for (large_desc& d : c->large_host) {
+    for (large_desc& d : set) {
         auto it = off.find(d.nbm.d);
         if (it == off.end() || d.nbm.d < 2 * d.S || !d.S) continue;
         std::string why;
         large_desc x;
         rc = build_large_desc(x, d.pair, d.LA, d.LB, d.nA, d.nB, c->prm.B, why, true,
-                              !c->large_no_direct && c->prm.edge_budget < (1ull << 28) &&   // 8-byte offsets < 2^31
+                              allow_direct && c->prm.edge_budget < (1ull << 28) &&   // 8-byte offsets < 2^31
                                   !slots_share_bucket(d.nbm.d, d.S, c->prm.B));
         if (rc) return fail(c, rc, why);
         x.g_head = it->second;
         x.g_next = it->second + cfg[d.nbm.d];
         d = x;
     }
+    return PVAC_OK;
+}
+
+// Shapes of the pairs ids[0, n) read back -> host descriptors on the dynamic layout (bucket counts
+// from this libstdc++), in pair order: a deterministic launch order (the kernels append ids in
+// arrival order). `out` is left empty on failure.
+int gather_large_descs(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_batch* B, const uint64_t* ids, uint64_t n,
+                       std::vector<large_desc>& out, const char* where) {
+    out.clear();
+    std::vector<uint64_t> info(5 * n);
+    hipError_t e = launch_gather_large(*A, *B, ids, n, c->large_info.get(), c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(info.data(), c->large_info.get(), info.size() * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return hip_fail(c, e, where);
+    out.resize(n);
+    for (uint64_t k = 0; k < n; ++k) {
+        std::string why;
+        const int rc = build_large_desc(out[k], info[5 * k], info[5 * k + 1], info[5 * k + 2], info[5 * k + 3],
+                                        info[5 * k + 4], c->prm.B, why);
+        if (rc) {
+            out.clear();
+            return fail(c, rc, why);
+        }
+    }
+    std::sort(out.begin(), out.end(), [](const large_desc& x, const large_desc& y) { return x.pair < y.pair; });
     return PVAC_OK;
 }
 
@@ -695,27 +576,8 @@ int pvac_hip_ct_mul_plan(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_
     plan->max_buckets = st.max_buckets;
     plan->max_layers = st.max_layers;
     if (st.n_large) {
-        // shapes of the general-path pairs -> host descriptors (bucket counts from this libstdc++)
-        std::vector<uint64_t> info(5 * st.n_large);
-        e = launch_gather_large(*A, *B, c->large_ids.get(), st.n_large, c->large_info.get(), c->stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(info.data(), c->large_info.get(), info.size() * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) return hip_fail(c, e, "ct_mul_plan (large)");
-        c->large_host.resize(st.n_large);
-        for (uint64_t k = 0; k < st.n_large; ++k) {
-            std::string why;
-            rc = build_large_desc(c->large_host[k], info[5 * k], info[5 * k + 1], info[5 * k + 2], info[5 * k + 3],
-                                  info[5 * k + 4], c->prm.B, why);
-            if (rc) {
-                c->large_host.clear();
-                return fail(c, rc, why);
-            }
-        }
-        // deterministic launch order (the plan kernel appends in arrival order)
-        std::sort(c->large_host.begin(), c->large_host.end(),
-                  [](const large_desc& x, const large_desc& y) { return x.pair < y.pair; });
-        rc = plan_static_groups(c);
+        rc = gather_large_descs(c, A, B, c->large_ids.get(), st.n_large, c->large_host, "ct_mul_plan (large)");
+        if (!rc) rc = assign_static_groups(c, c->large_host, true);
         if (rc) {
             c->large_host.clear();
             return rc;
@@ -727,12 +589,21 @@ int pvac_hip_ct_mul_plan(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_
 
 namespace {
 
-// A chain step's input held as dense images (ctx img_in, pvac_hip_ct_mul_chain) turned back into
-// hash-order records for the pairs given as (pair, |A.E|) before a path that reads A's records (the
-// non-direct kernels, the redo run). The device skips pairs whose flag is clear and clears the flags
-// of the pairs it converts.
-int images_to_records(pvac_hip_ctx* c, const pvac_ct_batch* A, const std::vector<std::pair<uint64_t, uint64_t>>& pn) {
-    if (!c->img_in || pn.empty()) return PVAC_OK;
+// A chain step's dense images (pvac_hip_ct_mul_chain; mul_large_args::A_img / C_img): per-pair flags
+// of A (read; cleared where A is turned back into records) and of C (written), and the counter of
+// pair-steps written as images. All null outside the chain.
+struct step_images {
+    uint32_t* in = nullptr;
+    uint32_t* out = nullptr;
+    unsigned long long* count = nullptr;
+};
+
+// A chain step's input held as dense images (img.in) turned back into hash-order records for the
+// pairs given as (pair, |A.E|) before a path that reads A's records (the non-direct kernels, the
+// redo run). The device skips pairs whose flag is clear and clears the flags of the pairs it converts.
+int images_to_records(pvac_hip_ctx* c, const pvac_ct_batch* A, const std::vector<std::pair<uint64_t, uint64_t>>& pn,
+                      step_images img) {
+    if (!img.in || pn.empty()) return PVAC_OK;
     std::vector<uint64_t> h(2 * pn.size());
     uint64_t tot = 0;
     for (size_t k = 0; k < pn.size(); ++k) {
@@ -745,110 +616,69 @@ int images_to_records(pvac_hip_ctx* c, const pvac_ct_batch* A, const std::vector
     if (rc) return rc;
     hipError_t e = hipMemcpyAsync(c->img_pairs.get(), h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess)
-        e = launch_image_to_records(*A, c->img_in, c->img_pairs.get(), (uint32_t)pn.size(), c->img_tmp.get(), c->prm.B,
+        e = launch_image_to_records(*A, img.in, c->img_pairs.get(), (uint32_t)pn.size(), c->img_tmp.get(), c->prm.B,
                                     c->img_grid_y, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // h is read from the host stack
     return e == hipSuccess ? PVAC_OK : hip_fail(c, e, "chain images to records");
 }
 
-// Runs the general path over the plan's large pairs in sub-batches that fit the scratch budget.
-int run_large(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_batch* B, const uint64_t* nonces,
-              pvac_ct_batch* C, uint32_t flags, uint32_t* salt_pos) {
-    const size_t nl = c->large_host.size();
+// Runs the general path over `set` (pair order, static groups assigned) in sub-batches that fit the
+// scratch budget (cut_sub_batch, large_plan.hpp).
+int run_large(pvac_hip_ctx* c, const std::vector<large_desc>& set, const pvac_ct_batch* A, const pvac_ct_batch* B,
+              const uint64_t* nonces, pvac_ct_batch* C, uint32_t flags, uint32_t* salt_pos, step_images img) {
+    const size_t nl = set.size();
     int rc = hip_fail(c, c->desc_dev.grow_floor(nl), "alloc large descriptors");
     if (!rc) rc = hip_fail(c, c->sel_dev.grow_floor(nl), "alloc large descriptor order");
     if (rc) return rc;
-    c->sel_host.resize(nl);
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 8ull << 30;
     uint64_t budget = std::max<uint64_t>((uint64_t)(free_b / 2) / 4 + c->arena.capacity(), 1ull << 24);
     budget = std::min<uint64_t>(budget, 16ull << 30);   // <= 64 GiB of scratch per sub-batch
     // a worker of pvac_hip_ct_mul_chain shares the device with the other workers: its share
     if (c->arena_cap_words) budget = std::min<uint64_t>(budget, std::max<uint64_t>(c->arena_cap_words, c->arena.capacity()));
-    c->large_exec = c->large_host;
+    sub_batch& sb = c->sub;
     size_t i = 0;
     while (i < nl) {
-        uint64_t words = 0;
-        size_t j = i;
-        uint64_t mS = 0, mZ = 0, mT = 0, mE = 0, mL = 0, mTa = 0, mLa = 0, mA = 0;
-        bool dyn = false, all_ib = true, any_dir = false, all_dir = true;
-        uint32_t mLBd = 0;
-        uint64_t n_ib = 0, n_dir = 0;   // path counters, added once the sub-batch has launched
-        while (j < nl && (j == i || words + c->large_exec[j].words <= budget) && j - i < 65535) {
-            large_desc& d = c->large_exec[j];
-            const uint64_t w = d.words;
-            rebase_desc(d, words);
-            words += w;
-            // direct pairs have no per-key scratch: the slot- and edge-sized grids are the others'
-            if (!d.direct) {
-                mS = std::max(mS, d.S);
-                mE = std::max(mE, d.capE);
-                mA = std::max<uint64_t>(mA, d.iblk ? d.nA : 0);
-            }
-            mZ = std::max(mZ, d.zero_words);
-            dyn |= d.g_head == kNoGrp;
-            all_ib &= d.iblk != 0;
-            any_dir |= d.direct != 0;
-            all_dir &= d.direct != 0;
-            n_ib += d.iblk;
-            n_dir += d.direct;
-            if (d.direct) mLBd = std::max<uint32_t>(mLBd, d.LB);
-            mL = std::max(mL, std::max<uint64_t>(d.Lc, (uint64_t)d.LA + d.LB));
-            ++j;
-        }
-        // products: pairs with few B layers (chain steps) take the A-layer-major kernel
-        uint32_t n_la = 0;
-        for (size_t k = i; k < j; ++k)
-            if (c->large_exec[k].LB <= kLaMaxLB) c->sel_host[i + n_la++] = (uint32_t)(k - i);
-        for (size_t k = i, q = n_la; k < j; ++k) {
-            const large_desc& d = c->large_exec[k];
-            const uint64_t tasks = (uint64_t)d.LA * d.LB;
-            mTa = std::max(mTa, tasks);
-            if (d.LB <= kLaMaxLB) {
-                mLa = std::max<uint64_t>(mLa, (d.LA + kLaPerWG - 1) / kLaPerWG);
-            } else {
-                mT = std::max(mT, tasks);
-                c->sel_host[i + q++] = (uint32_t)(k - i);
-            }
-        }
-        if (words > c->arena.capacity()) {
+        // the uploads below read sb's vectors when the stream reaches them: the previous sub-batch's
+        // must have been taken before its storage is cut anew
+        if (i && hipStreamSynchronize(c->stream) != hipSuccess) return hip_fail(c, hipErrorUnknown, "ct_mul_large");
+        cut_sub_batch(set, i, budget, sb);
+        if (sb.words > c->arena.capacity()) {
             // grow with 1/8 headroom (within the budget): batches of similar pairs differ by a few
             // words, and a free + re-malloc of tens of GB stalls for seconds
-            uint64_t grown = std::max<uint64_t>(words, std::min<uint64_t>(words + words / 8, budget));
+            uint64_t grown = std::max<uint64_t>(sb.words, std::min<uint64_t>(sb.words + sb.words / 8, budget));
             hipStreamSynchronize(c->stream);
             const auto t0 = std::chrono::steady_clock::now();
-            hipError_t e = c->arena.grow(words, grown);   // frees the old arena first
-            if (e == hipErrorOutOfMemory && grown > words) {   // without the headroom
+            hipError_t e = c->arena.grow(sb.words, grown);   // frees the old arena first
+            if (e == hipErrorOutOfMemory && grown > sb.words) {   // without the headroom
                 (void)hipGetLastError();
-                grown = words;
-                e = c->arena.grow(words, grown);
+                grown = sb.words;
+                e = c->arena.grow(sb.words, grown);
             }
-            if (e == hipErrorOutOfMemory && j - i > 1) {
+            if (e == hipErrorOutOfMemory && sb.end - i > 1) {
                 // other contexts hold the HBM the budget counted on: split this sub-batch and retry
                 (void)hipGetLastError();
-                for (size_t k = i; k < j; ++k) c->large_exec[k] = c->large_host[k];
-                budget = std::max<uint64_t>(words / 2, 1);
+                budget = std::max<uint64_t>(sb.words / 2, 1);
                 continue;
             }
             if (e != hipSuccess) return hip_fail(c, e, "alloc ct_mul scratch arena");
             if (std::getenv("PVAC_DEBUG_ARENA"))
                 std::fprintf(stderr, "[pvac] arena -> %.2f GB (free %.1f GB, sub-batch %zu pairs): %.1f ms\n",
-                             grown * 4e-9, free_b * 1e-9, j - i,
+                             grown * 4e-9, free_b * 1e-9, sb.end - i,
                              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
         }
-        hipError_t e = hipMemcpyAsync(c->desc_dev.get() + i, c->large_exec.data() + i, (j - i) * sizeof(large_desc),
+        hipError_t e = hipMemcpyAsync(c->desc_dev.get() + i, sb.desc.data(), sb.desc.size() * sizeof(large_desc),
                                       hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess)
-            e = hipMemcpyAsync(c->sel_dev.get() + i, c->sel_host.data() + i, (j - i) * sizeof(uint32_t), hipMemcpyHostToDevice,
+            e = hipMemcpyAsync(c->sel_dev.get() + i, sb.sel.data(), sb.sel.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
                                c->stream);
         if (e != hipSuccess) return hip_fail(c, e, "upload large descriptors");
-        mul_large_args a{};
+        mul_large_args a = sb.sizing;
         a.A = *A; a.B = *B; a.C = *C;
         a.nonces = nonces;
         a.pair_status = c->pair_status.get();
         a.desc = c->desc_dev.get() + i;
         a.scratch = c->arena.get();
-        a.nl = (uint32_t)(j - i);
         a.Bm = c->prm.B;
         a.canon_tag = c->prm.canon_tag;
         a.edge_budget = c->prm.edge_budget;
@@ -856,27 +686,17 @@ int run_large(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_batch* B, c
         a.salt_pos = salt_pos;
         a.grp = c->grp.get();
         a.sel = c->sel_dev.get() + i;
-        a.n_la = n_la;
-        a.max_S = mS; a.max_zero = mZ; a.max_tasks = mT; a.max_capE = mE; a.max_lay = mL;
-        a.max_tasks_all = mTa; a.max_la_wg = mLa; a.max_nA = mA;
-        a.any_dyn = dyn ? 1u : 0u;
-        a.all_iblk = all_ib ? 1u : 0u;
-        a.any_direct = any_dir ? 1u : 0u;
-        a.all_direct = all_dir ? 1u : 0u;
-        a.dir_lb = std::max<uint32_t>(mLBd, 1u);
         a.redo_ids = c->redo_ids.get();
         a.redo_cnt = c->redo_cnt.get();
-        a.A_img = c->img_in;
-        a.C_img = c->img_out;
-        a.img_count = c->img_out ? c->img_count : nullptr;
-        a.la_per_wg = kLaPerWG;
-        a.la_xcd = 0;
+        a.A_img = img.in;
+        a.C_img = img.out;
+        a.img_count = img.out ? img.count : nullptr;
         e = launch_ct_mul_large(a, c->stream);
         if (e != hipSuccess) return hip_fail(c, e, "ct_mul_large");
-        c->path_total[1] += j - i;
-        c->path_total[2] += n_ib;
-        c->path_total[3] += n_dir;
-        i = j;
+        c->path_total[1] += sb.end - i;
+        c->path_total[2] += sb.n_iblk;
+        c->path_total[3] += sb.n_direct;
+        i = sb.end;
     }
     return PVAC_OK;
 }
@@ -887,7 +707,7 @@ int run_large(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_batch* B, c
 // buckets is flagged too. Those pairs are re-run here on the general path's full layout, which
 // folds every sum before it orders keys.
 int redo_fresh_pairs(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_batch* B, const uint64_t* nonces,
-                     pvac_ct_batch* C, uint32_t flags, uint32_t* salt_pos) {
+                     pvac_ct_batch* C, uint32_t flags, uint32_t* salt_pos, step_images img) {
     unsigned int cnt = 0;
     hipError_t e = read_back(c, &cnt, c->redo_cnt.get(), sizeof cnt);
     if (e != hipSuccess) return hip_fail(c, e, "ct_mul_exec (redo count)");
@@ -895,59 +715,33 @@ int redo_fresh_pairs(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_batc
         c->redo_cnt_dirty = false;
         return PVAC_OK;
     }
-    std::vector<uint64_t> info(5 * (size_t)cnt);
-    e = launch_gather_large(*A, *B, c->redo_ids.get(), cnt, c->large_info.get(), c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(info.data(), c->large_info.get(), info.size() * 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return hip_fail(c, e, "ct_mul_exec (redo shapes)");
-    std::vector<large_desc> redo(cnt);
-    for (size_t k = 0; k < cnt; ++k) {
-        std::string why;
-        const int rc = build_large_desc(redo[k], info[5 * k], info[5 * k + 1], info[5 * k + 2], info[5 * k + 3],
-                                        info[5 * k + 4], c->prm.B, why);
-        if (rc) return fail(c, rc, why);
-    }
-    std::sort(redo.begin(), redo.end(), [](const large_desc& x, const large_desc& y) { return x.pair < y.pair; });
+    std::vector<large_desc> redo;
+    int rc = gather_large_descs(c, A, B, c->redo_ids.get(), cnt, redo, "ct_mul_exec (redo shapes)");
+    if (rc) return rc;
     // a chain step's image inputs become records first; the redo run reads and writes records only
-    uint32_t* const img_in = c->img_in;
-    uint32_t* const img_out = c->img_out;
-    if (img_in) {
+    if (img.in) {
         std::vector<std::pair<uint64_t, uint64_t>> pn;
         for (const large_desc& d : redo) pn.emplace_back(d.pair, d.nA);
-        const int rc = images_to_records(c, A, pn);
+        rc = images_to_records(c, A, pn, img);
         if (rc) return rc;
     }
-    c->img_in = nullptr;
-    c->img_out = nullptr;
-    struct img_restore {
-        pvac_hip_ctx* c;
-        uint32_t *in, *out;
-        ~img_restore() { c->img_in = in; c->img_out = out; }
-    } img_guard{c, img_in, img_out};
-    // run them as the context's large-pair set, then restore the plan's own set and its tables
-    std::vector<large_desc> plan_set;
-    plan_set.swap(c->large_host);
-    c->large_host.swap(redo);
-    c->large_no_direct = true;   // the exact path: per-key sums, no presence-based positions
-    int rc = plan_static_groups(c);
-    if (!rc) rc = run_large(c, A, B, nonces, C, flags, salt_pos);
+    // the exact path: per-key sums, no presence-based positions. The group tables become the redo
+    // set's, so the plan's own are rebuilt afterwards
+    rc = assign_static_groups(c, redo, false);
+    if (!rc) rc = run_large(c, redo, A, B, nonces, C, flags, salt_pos, {});
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = hip_fail(c, hipErrorUnknown, "ct_mul_exec (redo)");
-    c->large_no_direct = false;
-    c->large_host.swap(plan_set);
     if (!rc) {
         c->redo_total += cnt;
-        // the plan's own static group tables were replaced by the redo set's: rebuild them
-        if (!c->large_host.empty()) rc = plan_static_groups(c);
+        if (!c->large_host.empty()) rc = assign_static_groups(c, c->large_host, true);
     }
     // on failure the group tables may still belong to the redo set: no exec may reuse this plan
     if (rc) ++c->plan_stamp;
     return rc;
 }
 
-}  // namespace
-
-int pvac_hip_ct_mul_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_ct_batch* A, const pvac_ct_batch* B,
-                         const uint64_t* nonces, const uint64_t* salts, pvac_ct_batch* C, uint32_t flags) {
+// pvac_hip_ct_mul_exec, with a chain step's images (all null for a caller's batch)
+int ct_mul_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_ct_batch* A, const pvac_ct_batch* B,
+                const uint64_t* nonces, const uint64_t* salts, pvac_ct_batch* C, uint32_t flags, step_images img) {
     if (!c || !plan || plan->kind != 1 || !batch_ok(A) || !batch_ok(B) || !batch_ok(C))
         return fail(c, PVAC_EINVAL, "ct_mul_exec: bad arguments");
     if (A->n != plan->n_pairs || B->n != plan->n_pairs) return fail(c, PVAC_EINVAL, "ct_mul_exec: plan mismatch");
@@ -1020,28 +814,26 @@ int pvac_hip_ct_mul_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_
         // the direct mode emits hash order only: with the canonical order asked for, its pairs would
         // all be redone, so take them on the full layout from the start (descriptors rebuilt once;
         // the plan stays valid, its direct pairs now run the exact path)
-        c->large_no_direct = true;
-        const int rc = plan_static_groups(c);
-        c->large_no_direct = false;
+        const int rc = assign_static_groups(c, c->large_host, false);
         if (rc) {
             ++c->plan_stamp;
             return rc;
         }
     }
-    if (plan->n_large && c->img_in) {   // chain step: image inputs of pairs off the direct mode -> records
+    if (plan->n_large && img.in) {   // chain step: image inputs of pairs off the direct mode -> records
         std::vector<std::pair<uint64_t, uint64_t>> pn;
         for (const large_desc& d : c->large_host)
             if (!d.direct) pn.emplace_back(d.pair, d.nA);
-        const int rc = images_to_records(c, A, pn);
+        const int rc = images_to_records(c, A, pn, img);
         if (rc) return rc;
     }
     if (plan->n_large) {
         scoped_timer t(c, "ct_mul_large");
-        int rc = run_large(c, A, B, nonces, C, flags, salt_pos);
+        int rc = run_large(c, c->large_host, A, B, nonces, C, flags, salt_pos, img);
         if (rc) return rc;
     }
     {
-        int rc = redo_fresh_pairs(c, A, B, nonces, C, flags, salt_pos);
+        int rc = redo_fresh_pairs(c, A, B, nonces, C, flags, salt_pos, img);
         if (rc) return rc;
     }
     c->last_mul_pairs = A->n;
@@ -1051,6 +843,13 @@ int pvac_hip_ct_mul_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_
         if (e != hipSuccess) return hip_fail(c, e, "sigma");
     }
     return PVAC_OK;
+}
+
+}  // namespace
+
+int pvac_hip_ct_mul_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_ct_batch* A, const pvac_ct_batch* B,
+                         const uint64_t* nonces, const uint64_t* salts, pvac_ct_batch* C, uint32_t flags) {
+    return ct_mul_exec(c, plan, A, B, nonces, salts, C, flags, {});
 }
 
 int pvac_hip_ct_mul(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_batch* B, pvac_ct_batch* C,
@@ -1617,6 +1416,14 @@ struct chain_shared {
     }
 };
 
+// a HIP call of the chain's workers: a failure stops the chain with "ct_mul_chain: <where>: <error>"
+bool chain_ok(chain_shared* sh, hipError_t e, const char* where) {
+    if (e == hipSuccess) return true;
+    sh->failed(e == hipErrorOutOfMemory ? PVAC_ENOMEM : PVAC_EDEVICE,
+               std::string("ct_mul_chain: ") + where + ": " + hipGetErrorString(e));
+    return false;
+}
+
 struct chain_wstats {
     uint64_t gsum_pairs = 0, gsum_failed = 0, chunks = 0;
 };
@@ -1637,72 +1444,52 @@ pvac_ct_batch chain_view(const pvac_ct_batch& X, uint64_t c0, uint64_t k) {
 // copy, offsets by an exclusive scan, rows by k_stage_rows (peer reads when X lives elsewhere)
 bool stage_chunk(pvac_hip_ctx* k, chain_shared* sh, const pvac_ct_batch& src, pvac_ct_batch& out, chain_set& S) {
     const uint64_t kk = src.n;
-    auto hipchk = [&](hipError_t e, const char* where) {
-        if (e == hipSuccess) return true;
-        sh->failed(e == hipErrorOutOfMemory ? PVAC_ENOMEM : PVAC_EDEVICE,
-                   std::string("ct_mul_chain: stage ") + where + ": " + hipGetErrorString(e));
-        return false;
-    };
-    for (dev_stream_buf<uint64_t>* b : {&S.l_off, &S.l_cnt, &S.e_off, &S.e_cnt})
-        if (!hipchk(b->grow_headroom(kk, k->stream), "alloc")) return false;
+    if (!chain_ok(sh, S.grow_index(kk, k->stream), "stage alloc")) return false;
     if (ensure_pairs(k, kk)) {
         sh->failed(PVAC_ENOMEM, "ct_mul_chain: stage scratch: " + k->err);
         return false;
     }
     const int sd = sh->x_dev, dd = k->device;
-    if (!hipchk(hipMemcpyPeerAsync(S.l_cnt.get(), dd, src.l_cnt, sd, kk * 8, k->stream), "counts") ||
-        !hipchk(hipMemcpyPeerAsync(S.e_cnt.get(), dd, src.e_cnt, sd, kk * 8, k->stream), "counts") ||
-        !hipchk(hipMemcpyAsync(S.l_off.get(), S.l_cnt.get(), kk * 8, hipMemcpyDeviceToDevice, k->stream), "offsets") ||
-        !hipchk(hipMemcpyAsync(S.e_off.get(), S.e_cnt.get(), kk * 8, hipMemcpyDeviceToDevice, k->stream), "offsets") ||
-        !hipchk(launch_exclusive_scan_u64(S.l_off.get(), kk, k->scan_scratch.get(), &k->totals[0], k->stream), "scan") ||
-        !hipchk(launch_exclusive_scan_u64(S.e_off.get(), kk, k->scan_scratch.get(), &k->totals[1], k->stream), "scan"))
+    if (!chain_ok(sh, hipMemcpyPeerAsync(S.l_cnt.get(), dd, src.l_cnt, sd, kk * 8, k->stream), "stage counts") ||
+        !chain_ok(sh, hipMemcpyPeerAsync(S.e_cnt.get(), dd, src.e_cnt, sd, kk * 8, k->stream), "stage counts") ||
+        !chain_ok(sh, hipMemcpyAsync(S.l_off.get(), S.l_cnt.get(), kk * 8, hipMemcpyDeviceToDevice, k->stream), "stage offsets") ||
+        !chain_ok(sh, hipMemcpyAsync(S.e_off.get(), S.e_cnt.get(), kk * 8, hipMemcpyDeviceToDevice, k->stream), "stage offsets") ||
+        !chain_ok(sh, launch_exclusive_scan_u64(S.l_off.get(), kk, k->scan_scratch.get(), &k->totals[0], k->stream), "stage scan") ||
+        !chain_ok(sh, launch_exclusive_scan_u64(S.e_off.get(), kk, k->scan_scratch.get(), &k->totals[1], k->stream), "stage scan"))
         return false;
     unsigned long long tot[2] = {0, 0};
-    if (!hipchk(hipMemcpyAsync(tot, k->totals, sizeof tot, hipMemcpyDeviceToHost, k->stream), "totals") ||
-        !hipchk(hipStreamSynchronize(k->stream), "totals"))
+    if (!chain_ok(sh, hipMemcpyAsync(tot, k->totals, sizeof tot, hipMemcpyDeviceToHost, k->stream), "stage totals") ||
+        !chain_ok(sh, hipStreamSynchronize(k->stream), "stage totals"))
         return false;
-    if (!hipchk(S.layers.grow_headroom(tot[0], k->stream), "alloc layers")) return false;
+    if (!chain_ok(sh, S.layers.grow_headroom(tot[0], k->stream), "stage alloc layers")) return false;
     for (dev_stream_buf<uint64_t>* b : {&S.meta, &S.w_lo, &S.w_hi})
-        if (!hipchk(b->grow_headroom(tot[1], k->stream), "alloc edges")) return false;
-    out = pvac_ct_batch{};
-    out.n = kk;
-    out.l_off = S.l_off.get();
-    out.l_cnt = S.l_cnt.get();
-    out.layers = S.layers.get();
-    out.e_off = S.e_off.get();
-    out.e_cnt = S.e_cnt.get();
-    out.meta = S.meta.get();
-    out.w_lo = S.w_lo.get();
-    out.w_hi = S.w_hi.get();
-    return hipchk(launch_stage_rows(src, out, k->stream), "rows");
+        if (!chain_ok(sh, b->grow_headroom(tot[1], k->stream), "stage alloc edges")) return false;
+    out = S.view(kk);
+    return chain_ok(sh, launch_stage_rows(src, out, k->stream), "stage rows");
 }
 
 // the final step's sigmas (PVAC_MUL_WITH_SIGMA): salts from salts_at (or splitmix), then sigma_from_H
 // per edge over the finished hash-order output; a pair the exec put in the canonical order
 // (guard_budget / ORDER_CANONICAL) makes the step run once more with the salts mapped (exec's salt
-// positions), as pvac_hip_ct_mul_exec does for a batch
+// positions), as pvac_hip_ct_mul_exec does for a batch; that run reads A, which may still hold images
+// (a_img), and writes records
 bool chain_final_sigma(pvac_hip_ctx* k, chain_shared* sh, uint32_t d, uint64_t c0, pvac_hip_plan& plan,
-                       const pvac_ct_batch& A, const pvac_ct_batch& Xv, pvac_ct_batch& C, chain_set& S,
+                       const pvac_ct_batch& A, uint32_t* a_img, const pvac_ct_batch& Xv, pvac_ct_batch& C, chain_set& S,
                        uint32_t mflags) {
     const pvac_chain_opts& o = *sh->o;
-    auto hipchk = [&](hipError_t e, const char* where) {
-        if (e == hipSuccess) return true;
-        sh->failed(e == hipErrorOutOfMemory ? PVAC_ENOMEM : PVAC_EDEVICE,
-                   std::string("ct_mul_chain: sigma ") + where + ": " + hipGetErrorString(e));
-        return false;
-    };
     const uint64_t slots = std::max<uint64_t>(plan.total_edge_slots, 1);
     const uint32_t sw = k->prm.m_bits / 64;
-    if (!hipchk(S.sigma.grow(slots * sw, slots * sw, k->stream), "alloc (1 KiB per edge: a smaller chunk?)")) return false;
-    if (!hipchk(k->chain_salts.grow_headroom(slots, k->stream), "alloc salts")) return false;
+    if (!chain_ok(sh, S.sigma.grow(slots * sw, slots * sw, k->stream), "sigma alloc (1 KiB per edge: a smaller chunk?)")) return false;
+    if (!chain_ok(sh, k->chain_salts.grow_headroom(slots, k->stream), "sigma alloc salts")) return false;
     if (o.salts_at) {
         if (o.salts_at(o.user, d, c0, &A, &Xv, &C, k->chain_salts.get(), plan.total_edge_slots, (void*)k->stream) != 0) {
             sh->failed(PVAC_EINVAL, "ct_mul_chain: salts_at callback failed");
             return false;
         }
-    } else if (!hipchk(launch_fill_random(o.nonce_seed ^ 0x5A175A175A175A17ull ^ (97ull * c0 + d), k->chain_salts.get(), slots,
-                                          k->stream),
-                       "fill salts")) {
+    } else if (!chain_ok(sh,
+                         launch_fill_random(o.nonce_seed ^ 0x5A175A175A175A17ull ^ (97ull * c0 + d), k->chain_salts.get(), slots,
+                                            k->stream),
+                         "sigma fill salts")) {
         return false;
     }
     C.sigma = S.sigma.get();
@@ -1710,13 +1497,14 @@ bool chain_final_sigma(pvac_hip_ctx* k, chain_shared* sh, uint32_t d, uint64_t c
     bool hash_order = (mflags & PVAC_MUL_ORDER_CANONICAL) == 0;
     if (hash_order) {
         std::vector<uint32_t> stv(C.n);
-        if (!hipchk(hipMemcpyAsync(stv.data(), k->pair_status.get(), C.n * 4, hipMemcpyDeviceToHost, k->stream), "status") ||
-            !hipchk(hipStreamSynchronize(k->stream), "status"))
+        if (!chain_ok(sh, hipMemcpyAsync(stv.data(), k->pair_status.get(), C.n * 4, hipMemcpyDeviceToHost, k->stream), "sigma status") ||
+            !chain_ok(sh, hipStreamSynchronize(k->stream), "sigma status"))
             return false;
         for (uint32_t v : stv) hash_order &= v != 1u;
     }
-    if (hash_order) return hipchk(launch_sigma(k->H, k->prm, C, k->chain_salts.get(), nullptr, k->num_cus, k->stream), "launch");
-    if (pvac_hip_ct_mul_exec(k, &plan, &A, &Xv, k->chain_nonces.get(), k->chain_salts.get(), &C, mflags | PVAC_MUL_WITH_SIGMA)) {
+    if (hash_order) return chain_ok(sh, launch_sigma(k->H, k->prm, C, k->chain_salts.get(), nullptr, k->num_cus, k->stream), "sigma launch");
+    if (ct_mul_exec(k, &plan, &A, &Xv, k->chain_nonces.get(), k->chain_salts.get(), &C, mflags | PVAC_MUL_WITH_SIGMA,
+                    {a_img, nullptr, nullptr})) {
         sh->failed(PVAC_EDEVICE, "ct_mul_chain: sigma exec: " + k->err);
         return false;
     }
@@ -1740,12 +1528,6 @@ void chain_worker(pvac_hip_ctx* k, chain_shared* sh, chain_range* rg, bool stage
     // a caller hook or the gsum check reads every step's records; an image A never meets the fresh
     // kernel, whose pairs have at most kFreshEdgesMax < 2B edges a side
     const bool use_img = !check && !o.after_step && 2u * k->prm.B > kFreshEdgesMax;
-    auto hipchk = [&](hipError_t e, const char* where) {
-        if (e == hipSuccess) return true;
-        sh->failed(e == hipErrorOutOfMemory ? PVAC_ENOMEM : PVAC_EDEVICE,
-                   std::string("ct_mul_chain: ") + where + ": " + hipGetErrorString(e));
-        return false;
-    };
     auto rcchk = [&](int rc, const char* where) {
         if (rc == PVAC_OK) return true;
         sh->failed(rc, std::string("ct_mul_chain: ") + where + ": " + k->err);
@@ -1762,10 +1544,6 @@ void chain_worker(pvac_hip_ctx* k, chain_shared* sh, chain_range* rg, bool stage
         pvac_ct_batch A = Xv;
         int cur = 0;
         uint32_t* a_img = nullptr;   // the previous step's image flags (A's)
-        struct img_reset {
-            pvac_hip_ctx* k;
-            ~img_reset() { k->img_in = k->img_out = nullptr; }
-        } img_guard{k};
         for (uint32_t d = 0; d < o.depth; ++d) {
             if (sh->stop.load()) return;
             // this step's operand: operands[d] (the reference's loop multiplies by a fresh enc_value per
@@ -1777,17 +1555,8 @@ void chain_worker(pvac_hip_ctx* k, chain_shared* sh, chain_range* rg, bool stage
                     return;
             }
             chain_set& S = k->chain_bufs[cur];
-            if (!hipchk(S.l_off.grow_headroom(kk, k->stream), "alloc offsets") ||
-                !hipchk(S.l_cnt.grow_headroom(kk, k->stream), "alloc counts") ||
-                !hipchk(S.e_off.grow_headroom(kk, k->stream), "alloc offsets") ||
-                !hipchk(S.e_cnt.grow_headroom(kk, k->stream), "alloc counts"))
-                return;
-            pvac_ct_batch C{};
-            C.n = kk;
-            C.l_off = S.l_off.get();
-            C.l_cnt = S.l_cnt.get();
-            C.e_off = S.e_off.get();
-            C.e_cnt = S.e_cnt.get();
+            if (!chain_ok(sh, S.grow_index(kk, k->stream), "alloc offsets / counts")) return;
+            pvac_ct_batch C = S.view(kk);   // the plan writes its offsets and counts; the rows are sized below
             pvac_hip_plan plan{};
             if (!rcchk(pvac_hip_ct_mul_plan(k, &A, &Xv, &C, &plan), "plan")) return;
             // an output array that does not fit first takes this worker's scratch arena back (the
@@ -1800,7 +1569,7 @@ void chain_worker(pvac_hip_ctx* k, chain_shared* sh, chain_range* rg, bool stage
                     k->arena.release();
                     if (e == hipSuccess) e = b.grow_headroom(need, k->stream);
                 }
-                return hipchk(e, what);
+                return chain_ok(sh, e, what);
             };
             if (!grow_out(S.layers, plan.total_layer_slots, "alloc layers") ||
                 !grow_out(S.meta, plan.total_edge_slots, "alloc edges") ||
@@ -1808,11 +1577,8 @@ void chain_worker(pvac_hip_ctx* k, chain_shared* sh, chain_range* rg, bool stage
                 !grow_out(S.w_hi, plan.total_edge_slots, "alloc edges"))
                 return;
             const size_t nw = 2 * std::max<uint64_t>(plan.total_layer_slots, 1);
-            if (!hipchk(k->chain_nonces.grow_headroom(nw, k->stream), "alloc nonces")) return;
-            C.layers = S.layers.get();
-            C.meta = S.meta.get();
-            C.w_lo = S.w_lo.get();
-            C.w_hi = S.w_hi.get();
+            if (!chain_ok(sh, k->chain_nonces.grow_headroom(nw, k->stream), "alloc nonces")) return;
+            C = S.view(kk);
             if (o.nonces_at) {
                 if (o.nonces_at(o.user, d, c0, &A, &Xv, &C, k->chain_nonces.get(), nw, (void*)k->stream) != 0) {
                     sh->failed(PVAC_EINVAL, "ct_mul_chain: nonces_at callback failed");
@@ -1823,22 +1589,19 @@ void chain_worker(pvac_hip_ctx* k, chain_shared* sh, chain_range* rg, bool stage
                     sh->failed(PVAC_EINVAL, "ct_mul_chain: fill_nonces callback failed");
                     return;
                 }
-            } else if (!hipchk(launch_fill_random(o.nonce_seed + 97ull * c0 + d, k->chain_nonces.get(), nw, k->stream),
+            } else if (!chain_ok(sh, launch_fill_random(o.nonce_seed + 97ull * c0 + d, k->chain_nonces.get(), nw, k->stream),
                                "fill nonces")) {
                 return;
             }
             uint32_t* c_img = nullptr;
             if (use_img && d + 1 < o.depth) {
-                if (!hipchk(S.img.grow_headroom(kk, k->stream), "alloc image flags")) return;
-                if (!hipchk(hipMemsetAsync(S.img.get(), 0, kk * 4, k->stream), "image flags")) return;
+                if (!chain_ok(sh, S.img.grow_headroom(kk, k->stream), "alloc image flags")) return;
+                if (!chain_ok(sh, hipMemsetAsync(S.img.get(), 0, kk * 4, k->stream), "image flags")) return;
                 c_img = S.img.get();
             }
-            k->img_in = a_img;
-            k->img_out = c_img;
-            k->img_count = k->chain_stats.get() + 2 * PVAC_CHAIN_MAX_DEPTH;
-            if (!rcchk(pvac_hip_ct_mul_exec(k, &plan, &A, &Xv, k->chain_nonces.get(), nullptr, &C, mflags), "exec")) return;
-            k->img_out = nullptr;   // the final-step sigma re-run below reads A (img_in), writes records
-            if (!hipchk(launch_chain_stats(A, Xv, C, k->chain_stats.get() + 2 * d, k->stream), "stats")) return;
+            const step_images img{a_img, c_img, k->chain_stats.get() + 2 * PVAC_CHAIN_MAX_DEPTH};
+            if (!rcchk(ct_mul_exec(k, &plan, &A, &Xv, k->chain_nonces.get(), nullptr, &C, mflags, img), "exec")) return;
+            if (!chain_ok(sh, launch_chain_stats(A, Xv, C, k->chain_stats.get() + 2 * d, k->stream), "stats")) return;
             if (check) {
                 uint64_t bad = 0;
                 if (!rcchk(pvac_hip_check_mul_gsum(k, &A, &Xv, &C, k->chain_nonces.get(), nullptr, &bad), "gsum check"))
@@ -1850,8 +1613,7 @@ void chain_worker(pvac_hip_ctx* k, chain_shared* sh, chain_range* rg, bool stage
                 sh->failed(PVAC_EINVAL, "ct_mul_chain: after_step callback failed");
                 return;
             }
-            if (sigma && d + 1 == o.depth && !chain_final_sigma(k, sh, d, c0, plan, A, Xv, C, S, mflags)) return;
-            k->img_in = nullptr;
+            if (sigma && d + 1 == o.depth && !chain_final_sigma(k, sh, d, c0, plan, A, a_img, Xv, C, S, mflags)) return;
             a_img = c_img;
             A = C;
             cur ^= 1;
@@ -1864,14 +1626,14 @@ void chain_worker(pvac_hip_ctx* k, chain_shared* sh, chain_range* rg, bool stage
             pvac_ct_batch H = A;
             H.n = m;
             auto put = [&](uint64_t* to) {
-                if (kind == 1) return hipchk(launch_batch_digest(H, to, k->stream), "digest");
-                if (kind == 2) return hipchk(launch_batch_sumdigest(H, to, k->stream), "sum digest");
-                return hipchk(hipMemcpyAsync(to, A.e_cnt, m * 8, hipMemcpyDeviceToDevice, k->stream), "counts");
+                if (kind == 1) return chain_ok(sh, launch_batch_digest(H, to, k->stream), "digest");
+                if (kind == 2) return chain_ok(sh, launch_batch_sumdigest(H, to, k->stream), "sum digest");
+                return chain_ok(sh, hipMemcpyAsync(to, A.e_cnt, m * 8, hipMemcpyDeviceToDevice, k->stream), "counts");
             };
             if (!remote) return put(dst + c0);
-            if (!hipchk(k->chain_out.grow_headroom(m, k->stream), "alloc outputs") || !put(k->chain_out.get()))
+            if (!chain_ok(sh, k->chain_out.grow_headroom(m, k->stream), "alloc outputs") || !put(k->chain_out.get()))
                 return false;
-            return hipchk(hipMemcpyPeerAsync(dst + c0, sh->x_dev, k->chain_out.get(), k->device, m * 8, k->stream), "peer copy");
+            return chain_ok(sh, hipMemcpyPeerAsync(dst + c0, sh->x_dev, k->chain_out.get(), k->device, m * 8, k->stream), "peer copy");
         };
         if (!out_words(o.digest_n, o.digest_out, 1) || !out_words(o.count_n, o.count_out, 0) ||
             !out_words(o.sumdigest_n, o.sumdigest_out, 2))
@@ -2032,7 +1794,10 @@ int pvac_hip_ct_mul_chain(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac_ch
         pvac_hip_ctx* k = c->chain_kids[w];
         hipSetDevice(k->device);
         e = hipStreamSynchronize(k->stream);
-        if (e != hipSuccess && sh.rc == PVAC_OK) sh.failed(PVAC_EDEVICE, std::string("ct_mul_chain: ") + hipGetErrorString(e));
+        if (e != hipSuccess && sh.rc == PVAC_OK) {
+            hip_fail(c, e, "ct_mul_chain");
+            sh.failed(PVAC_EDEVICE, c->err);
+        }
         unsigned long long v[2 * PVAC_CHAIN_MAX_DEPTH + 1];
         if (hipMemcpy(v, k->chain_stats.get(), sizeof v, hipMemcpyDeviceToHost) == hipSuccess) {
             for (uint32_t d = 0; d < o->depth; ++d) {
