@@ -239,7 +239,7 @@ hipError_t launch_add_merge(const pvac_ct_batch& A, const pvac_ct_batch& B, pvac
                             const merge_pair_info& info, uint32_t Bm, int negate_b, void* scratch, size_t scratch_bytes,
                             unsigned long long* counters, hipStream_t st);
 
-// ---- ct_mul, general path (k_mul_large.hip): multi-kernel, global scratch, one workgroup
+// ---- ct_mul, general path (k_mul_large.hip and the k_large_* files): multi-kernel, global scratch, one workgroup
 // per (A-layer, B-layer) product task. The host prepares one descriptor per large pair with
 // ABSOLUTE u32-word offsets into one scratch arena (64-bit arrays on even offsets).
 constexpr uint32_t kLargeLayersMax = 16384;   // |A.L| + |B.L| + |A.L||B.L| handled in LDS
@@ -268,14 +268,13 @@ struct large_desc {
     // full layout. Its A ids carry the dense cell (k_large_lists)
     uint32_t direct;
     uint32_t pad_d;
-    uint64_t nb_m;               // floor(2^32 / |B.E|): t / |B.E| by div_small (k_mul_large.hip)
+    uint64_t nb_m;               // floor(2^32 / |B.E|): t / |B.E| by div_small (k_large.hpp)
     // static bucket groups (bucket_count >= 2 S): per-slot chain head / next of the slots sharing
     // a libstdc++ bucket, word offsets into mul_large_args::grp (kNoGrp: dynamic chains via link)
     uint64_t g_head, g_next;
     // zero-initialised block [o_zero, o_zero + zero_words): cnt | hkey | hhead | bmask | bcnt | used
     uint64_t o_zero, zero_words;
-    uint64_t o_cnt;              // [16] neA, neB, invalid, total edges, canonical, A / B id allocation, deferred tasks,
-                                 // [kCntIFail] per-A-edge order abandoned (iblk pairs)
+    uint64_t o_cnt;              // [kCntWords] the pair's counters and flags, words kCntNeA .. kCntImg (below)
     uint64_t o_hkey;             // [2^hbits] u64 bucket ids + 1
     uint64_t o_hhead;            // [2^hbits] chain heads (slot + 1)
     uint64_t o_bmask;            // [nblk] u64 per 16 first-insert times: bucket-leader edge codes (2 bits
@@ -289,7 +288,7 @@ struct large_desc {
     uint64_t o_lstA, o_lstB;     // [2 LA] start,count per layer ++ [nA] edge ids; same for B
     uint64_t o_neA, o_neB;       // [LA] / [LB] non-empty layer lists
     uint64_t o_defer;            // [LA LB] tasks k_large_products_la leaves to k_large_products_defer
-                                 // (la << 16 | lb index), counted in cnt[7]
+                                 // (la << 16 | lb index), counted in cnt[kCntDefer]
     uint64_t o_info;             // [S] ebits (2 bits) | hash slot << 2
     uint64_t o_sums;             // [S] x 4 u64: P lo, P hi, M lo, M hi
     uint64_t o_nxt;              // [S] bucket chain links
@@ -363,7 +362,7 @@ hipError_t launch_ct_mul_large(const mul_large_args& a, hipStream_t st);
 hipError_t launch_image_to_records(const pvac_ct_batch& A, uint32_t* img, const uint64_t* pairs, uint32_t n_pairs,
                                    uint64_t* tmp, uint32_t Bm, uint32_t y_cap, hipStream_t st);
 __host__ __device__ inline uint32_t al16(uint32_t x) { return (x + 15u) & ~15u; }
-// matrix-core dense mode (k_mul_large.hip): a task's sparse side is staged as prec | pinf
+// matrix-core dense mode (k_large_mx.hpp): a task's sparse side is staged as prec | pinf
 constexpr int kMxKS = 10;                          // k-steps held in registers: 2 sparse edges each
 constexpr uint32_t kMxMaxSparse = 2u * kMxKS;      // sparse sides up to this size take the MFMA path
 constexpr uint32_t kMxSparseBytes = 64u * kMxMaxSparse;
@@ -394,7 +393,15 @@ hipError_t launch_chain_stats(const pvac_ct_batch& A, const pvac_ct_batch& X, co
                               unsigned long long* out, hipStream_t st);
 constexpr uint64_t kNoGrp = ~0ull;
 constexpr uint32_t kCntWords = 16;    // large_desc::o_cnt words
-constexpr uint32_t kCntIFail = 8;     // cnt word: an iblk pair uses the block marks after all
+constexpr uint32_t kCntNeA = 0;       // cnt word: non-empty A layers (length of o_neA)
+constexpr uint32_t kCntNeB = 1;       // cnt word: non-empty B layers (length of o_neB)
+constexpr uint32_t kCntInvalid = 2;   // cnt word: the pair has invalid edges and is rejected (k_large_lists)
+constexpr uint32_t kCntTotal = 3;     // cnt word: total output edges (k_large_scan / k_large_scan_direct)
+constexpr uint32_t kCntCanonical = 4; // cnt word: the pair takes the canonical (layer, idx, P<M) order
+constexpr uint32_t kCntAllocA = 5;    // cnt word: A edge ids allocated to layer lists (k_large_lists)
+constexpr uint32_t kCntAllocB = 6;    // cnt word: B edge ids allocated to layer lists
+constexpr uint32_t kCntDefer = 7;     // cnt word: tasks in o_defer (k_large_products_la -> _defer)
+constexpr uint32_t kCntIFail = 8;    // cnt word: an iblk pair uses the block marks after all
 constexpr uint32_t kCntIShared = 9;   // cnt word: an iblk pair has keys sharing a bucket (order probes)
 constexpr uint32_t kCntDirect = 10;   // cnt word: a direct pair's positions are final (k_large_scan_direct)
 constexpr uint32_t kCntRedo = 11;     // cnt word: a direct pair was handed to the host's redo

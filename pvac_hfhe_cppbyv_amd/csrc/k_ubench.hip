@@ -167,7 +167,7 @@ __global__ __launch_bounds__(kUB) void k_probe_col26(uint64_t* out, uint32_t ite
     out[(uint64_t)blockIdx.x * kUB + threadIdx.x] = r;
 }
 
-// the matrix-core product ceiling of the general path's dense mode (k_mul_large.hip): back-to-back
+// the matrix-core product ceiling of the general path's dense mode (k_large_mx.hpp): back-to-back
 // v_mfma_i32_32x32x32_i8 on four independent accumulators per wave; one such MFMA is 64 Fp
 // products there (32 output rows x 2 sparse edges, 16 x 16 digit pairs each)
 typedef int pb_v4 __attribute__((ext_vector_type(4)));

@@ -60,7 +60,7 @@ inline int build_large_desc(large_desc& d, uint64_t pair, uint64_t LA, uint64_t 
     d.nbm = make_fastmod64(bucket_count_after_reserve(d.n));
     d.hbits = std::max<uint32_t>(1, ceil_log2(2 * std::max<uint64_t>(keys, 1)));
     d.g_head = d.g_next = kNoGrp;
-    // per-A-edge emit order (k_mul_large.hip): static groups and the A-layer-major products kernel
+    // per-A-edge emit order (k_large_products.hip): static groups and the A-layer-major products kernel
     d.iblk = static_grp && LB <= kLaMaxLB && nA >= 1 && nB >= 1 && nB <= kIblkMaxNB ? 1u : 0u;
     // (direct A ids and writer lists pack an A edge with its dense cell: A edges < 2^21, 2 B <= 2^11)
     // (and k_large_products_direct's LDS: the digit table, LB staged B layers and their sums)

@@ -1,4 +1,4 @@
-"""GPU parity of the general ct_mul path (k_mul_large.hip): chains c_k = c_{k-1} * x_k
+"""GPU parity of the general ct_mul path (k_mul_large.hip, k_large_*.hip): chains c_k = c_{k-1} * x_k
 (reference tests/test_main.cpp:289-295), squares c <- c * c (tests/test_depth.cpp:46), pairs the
 fresh kernel cannot hold, mixed batches, duplicate edges, guard_budget ordering. Bit-exact
 against the reference's golden fixtures and the pinned CPU oracle."""
@@ -343,7 +343,7 @@ def _mk_layers(rng, counts, dup_layers=(), B=337):
 
 @pytest.mark.parametrize("all_iblk", [False, True])
 def test_iblk_order_and_fallbacks_vs_oracle(oracle, all_iblk):
-    """Per-A-edge emit order (k_mul_large.hip iblk_layer / order): chain-step shapes (dense A layers
+    """Per-A-edge emit order (k_large_products.hip iblk_layer, k_mul_large.hip order): chain-step shapes (dense A layers
     x B layers of <= 20 edges, |B.E| up to 63, keys sharing libstdc++ buckets) bit-exact vs the
     oracle, next to the pairs that must fall back to the block marks inside the same batch: a B
     layer of 21+ edges, an A layer with duplicate (idx, ch) cells, an A layer below the dense
@@ -630,3 +630,31 @@ def test_direct_pairs_canonical_flag_no_redo(oracle):
     assert eng.ct_mul_path_counts()["direct"] - p1["direct"] == 3 and eng.ct_mul_redo_count() == r0
     for p in range(3):
         _same(out2[p], oracle.ct_mul(xs[p], ys[p], per2[p], canon_tag=0xCA71), view=False)
+
+
+def test_mx_kstep_counts_vs_oracle(oracle):
+    """Every k-step count of both matrix-core row loops (mx_blocks_n / dir_rows_n <1..10>, one
+    instantiation per count of two-edge k-steps): ten pairs of three saturated A layers (|A.E| =
+    2,022, which keeps the bucket count at 22,447 .. 67,307 with no key slots sharing a bucket, so
+    every pair is direct-eligible) times two B layers whose sizes cover 1..20 once each: every
+    k-step count with and without the zero padding edge. Default flags: all ten pairs run the direct
+    mode (k_large_products_direct), none is redone. MUL_ORDER_CANONICAL on the same engine and
+    batch: none is direct, all ten go through k_large_products_la with the iblk records, canonical
+    order. Both bit-exact vs the oracle."""
+    from pvac_hfhe_cppbyv_amd import Engine, MUL_ORDER_CANONICAL
+    rng = np.random.default_rng(0x4B57)
+    sizes = [(1, 10), (2, 9), (3, 8), (4, 7), (5, 6), (11, 20), (12, 19), (13, 18), (14, 17), (15, 16)]
+    xs = [_mk_layers(rng, [674, 674, 674]) for _ in sizes]
+    ys = [_mk_layers(rng, list(s)) for s in sizes]
+    eng = Engine(device=0, canon_tag=0x4B58)
+    p0, r0 = eng.ct_mul_path_counts(), eng.ct_mul_redo_count()
+    out, plan, per = _run_mul(eng, xs, ys, seed=0x4B59)
+    p1 = eng.ct_mul_path_counts()
+    assert plan.n_large == 10
+    assert p1["direct"] - p0["direct"] == 10 and eng.ct_mul_redo_count() == r0
+    for p in range(10):
+        _same(out[p], oracle.ct_mul(xs[p], ys[p], per[p], canon_tag=0x4B58), view=False)
+    out2, _, per2 = _run_mul(eng, xs, ys, seed=0x4B59, flags=MUL_ORDER_CANONICAL)
+    assert eng.ct_mul_path_counts()["direct"] == p1["direct"] and eng.ct_mul_redo_count() == r0
+    for p in range(10):
+        _same(out2[p], oracle.ct_mul(xs[p], ys[p], per2[p], canon_tag=0x4B58, edge_budget=0), view=False)

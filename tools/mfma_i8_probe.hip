@@ -1,5 +1,5 @@
 // mfma_i8_probe.hip — checks the operand / result lane maps of v_mfma_i32_32x32x32_i8 that
-// k_mul_large.hip's matrix-core products rely on, with random signed bytes on both operands:
+// the general path's matrix-core products (k_large_mx.hpp) rely on, with random signed bytes on both operands:
 //   A (M x K): lane l holds A[m = l & 31][k = (h = l >> 5, byte j)]
 //   B (K x N): lane l holds B[k = (h, j)][n = l & 31]
 //   D (M x N): lane l, register i holds D[m = (i & 3) + 8 (i >> 2) + 4 (l >> 5)][n = l & 31]
