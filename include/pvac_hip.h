@@ -101,7 +101,7 @@ typedef struct pvac_hip_plan {
     uint64_t n_large;             /* pairs served by the layer-dense path */
     uint64_t n_invalid;           /* reserved, always 0: rejections are per pair, see pvac_hip_ct_mul_status */
     uint32_t max_keys, max_prod, max_na, max_nb, max_buckets, max_layers;  /* launch sizing */
-    uint32_t kind;                /* 1 = mul, 2 = add, 3 = sub */
+    uint32_t kind;                /* 1 = mul, 2 = add, 3 = sub, 4 = recrypt, 5 = compact */
     uint32_t reserved[5];
 } pvac_hip_plan;
 
@@ -361,6 +361,52 @@ int pvac_hip_ct_scale(pvac_hip_ctx* ctx, pvac_ct_batch* X, uint64_t s_lo, uint64
 /* sigma_from_H for every edge of a batch (crypto/matrix.hpp:267-303): sigma of edge slot e
  * from its layer's (ztag, nonce), idx, ch and salts[e]. Requires H (set_H / gen_H). */
 int pvac_hip_sigma_batch(pvac_hip_ctx* ctx, pvac_ct_batch* X, const uint64_t* salts);
+
+/* ---------------------------------------------------------------- ct_recrypt and its parts
+ * pk.ubk.inv (gen_ubk_public, crypto/matrix.hpp:95-164; core/types.hpp:81-84) from HOST memory.
+ * PVAC_EINVAL unless inv is a permutation of [0, m_bits) and m_bits is the context's. Synchronous. */
+int pvac_hip_ctx_set_ubk(pvac_hip_ctx* ctx, const int32_t* inv_host, uint32_t m_bits);
+/* sigma_density's numerator (ops/encrypt.hpp:29-37): ones[i] (DEVICE, n u64) = sum of popcnt over
+ * the ceil(m_bits / 64) words of cipher i's e_cnt[i] sigma rows; the density is
+ * ones / (e_cnt * m_bits), computed by the caller (the reference divides in long double). */
+int pvac_hip_sigma_popcount(pvac_hip_ctx* ctx, const pvac_ct_batch* X, uint64_t* ones);
+/* ubk_apply (crypto/matrix.hpp:167-188, 306-310), in place on every sigma row:
+ * out[inv[src]] = in[src] for src < m_bits. active (DEVICE, n u32, nullable): a cipher with
+ * active[i] == 0 is left untouched. Needs set_ubk. */
+int pvac_hip_ubk_apply(pvac_hip_ctx* ctx, pvac_ct_batch* X, const uint32_t* active);
+/* compact_edges then compact_layers (ops/encrypt.hpp:39-104) of every cipher of X into C (C's arrays
+ * are not X's). The plan writes C->l_off / C->e_off as exclusive scans of X's counts (the output is
+ * never larger) and fills *plan (kind 5; synchronises once); the caller allocates C's rows and sigma
+ * (total_layer_slots / total_edge_slots), exec writes the rows and C->l_cnt / C->e_cnt. Edges of one
+ * (layer, idx, ch) are merged: the weight is the sequential fp_add chain from 0 in edge order
+ * (non-canonical addends included, field.hpp:53-55), the sigma their XOR; a group is dropped only
+ * when both are zero; the output is sorted by (layer, idx, P before M). An edge whose layer or idx is
+ * out of range (undefined in the reference) is dropped. X and C must carry sigma (PVAC_EINVAL).
+ * A cipher whose key space |L| * 2B is at most 14336 cells (21 layers at B = 337), with at most
+ * 1024 layers and 65536 edges, is served by one workgroup of a batched kernel; any other by the
+ * per-cipher merge path of ct_add's guard_budget. exec takes this context's latest plan only. */
+int pvac_hip_compact_plan(pvac_hip_ctx* ctx, const pvac_ct_batch* X, pvac_ct_batch* C, pvac_hip_plan* plan);
+int pvac_hip_compact_exec(pvac_hip_ctx* ctx, const pvac_hip_plan* plan, const pvac_ct_batch* X, pvac_ct_batch* C);
+/* Ciphers compacted since the context was created (compact_exec and ct_recrypt_exec): out[0] by the
+ * batched kernel, out[1] by the merge path. */
+int pvac_hip_compact_path_count(pvac_hip_ctx* ctx, uint64_t out[2]);
+/* ct_recrypt (ops/recrypt.hpp:26-41) of every cipher of X against the zero pool `pool`
+ * (ek.zero_pool as a batch; pool->n = 0 is the empty pool). The plan writes C->l_off / C->e_off for
+ * per-cipher capacities |X.L| + 8 max|pool.L| and |X.E| + 8 max|pool.E|, zeroes C->l_cnt / C->e_cnt
+ * when given, and fills *plan (kind 4; max_layers / max_nb hold the pool's largest layer and edge
+ * counts, and exec rejects a larger pool; synchronises once). exec, per cipher: up to 8 times, while
+ * its sigma density lies outside [0.495, 0.505] (decided on the host from the exact popcounts with
+ * the reference's long double expression), ct_add the pool member picks[8 i + it] % pool->n
+ * (pvac_hip_ct_add_plan / _exec, guard_budget included), then ubk_apply; at the end compact_edges
+ * and compact_layers, always. picks (HOST, 8 n words) replace the loop's csprng_u64 draws
+ * (recrypt.hpp:32): only the iterations that run consume theirs, in order. iters (HOST, n u32,
+ * nullable) receives the iteration counts. An empty pool or e_cnt[i] == 0 copies cipher i verbatim,
+ * uncompacted (recrypt.hpp:27). Needs set_ubk and sigma on X, pool and C (PVAC_EINVAL), all of one
+ * even sigma_words. Intermediate results live in buffers the context owns. Synchronous. */
+int pvac_hip_ct_recrypt_plan(pvac_hip_ctx* ctx, const pvac_ct_batch* X, const pvac_ct_batch* pool, pvac_ct_batch* C,
+                             pvac_hip_plan* plan);
+int pvac_hip_ct_recrypt_exec(pvac_hip_ctx* ctx, const pvac_hip_plan* plan, const pvac_ct_batch* X,
+                             const pvac_ct_batch* pool, const uint64_t* picks, pvac_ct_batch* C, uint32_t* iters);
 
 /* ---------------------------------------------------------------- synthetic inputs / checks
  * Fresh-shaped cipher generator used by bench.py (SURVEY §8(d) cfg 3 generator): per cipher

@@ -830,6 +830,127 @@ public:
         return r;
     }
 
+    // pk.ubk.inv (gen_ubk_public, crypto/matrix.hpp:95-164), uploaded once per engine.
+    template <class PubKeyT>
+    void ensure_ubk(const PubKeyT& pk) {
+        if (ubk_ready_) return;
+        const std::vector<int32_t> inv(pk.ubk.inv.begin(), pk.ubk.inv.end());
+        check(pvac_hip_ctx_set_ubk(ctx_, inv.data(), (uint32_t)inv.size()));
+        ubk_ready_ = true;
+    }
+
+    // sigma_density (ops/encrypt.hpp:29-37) per cipher: the exact popcounts from the device, the
+    // reference's long double quotient on the host.
+    template <class CipherT>
+    std::vector<double> sigma_density(const std::vector<const CipherT*>& cs) {
+        const size_t n = cs.size();
+        if (!n) return {};
+        detail::batch x;
+        detail::to_host(cs, sigma_words(), true, x);
+        detail::upload(x, stream_, true);
+        pvac_ct_batch vx = x.view(true);
+        detail::dev_array<uint64_t> ones(n);
+        check(pvac_hip_sigma_popcount(ctx_, &vx, ones.p));
+        const detail::hvec<uint64_t> o = detail::d2h_u64(ones.p, n, stream_);
+        std::vector<double> d(n, 0.0);
+        for (size_t i = 0; i < n; ++i) {
+            if (cs[i]->E.empty()) continue;
+            long double total = 0;
+            for (size_t k = 0; k < cs[i]->E.size(); ++k) total += prm_.m_bits;
+            d[i] = (double)((long double)o[i] / total);
+        }
+        return d;
+    }
+
+    // ubk_apply (crypto/matrix.hpp:306-310) on copies of the ciphers.
+    template <class PubKeyT, class CipherT>
+    std::vector<CipherT> ubk_apply(const PubKeyT& pk, const std::vector<const CipherT*>& cs) {
+        const size_t n = cs.size();
+        if (!n) return {};
+        ensure_ubk(pk);
+        detail::batch x;
+        detail::to_host(cs, sigma_words(), true, x);
+        detail::upload(x, stream_, true);
+        pvac_ct_batch vx = x.view(true);
+        check(pvac_hip_ubk_apply(ctx_, &vx, nullptr));
+        return detail::from_device<CipherT>(x, n, x.layers.size(), x.meta.size(), prm_.m_bits, true, stream_);
+    }
+
+    // compact_edges then compact_layers (ops/encrypt.hpp:39-104).
+    template <class CipherT>
+    std::vector<CipherT> compact(const std::vector<const CipherT*>& cs) {
+        const size_t n = cs.size();
+        if (!n) return {};
+        detail::batch x, c;
+        detail::to_host(cs, sigma_words(), true, x);
+        detail::upload(x, stream_, true);
+        pvac_ct_batch vx = x.view(true);
+        c.d_l_off.alloc(n); c.d_l_cnt.alloc(n); c.d_e_off.alloc(n); c.d_e_cnt.alloc(n);
+        pvac_ct_batch vc{};
+        vc.l_off = c.d_l_off.p; vc.l_cnt = c.d_l_cnt.p; vc.e_off = c.d_e_off.p; vc.e_cnt = c.d_e_cnt.p;
+        pvac_hip_plan plan{};
+        check(pvac_hip_compact_plan(ctx_, &vx, &vc, &plan));
+        detail::alloc_out(c, n, std::max<uint64_t>(plan.total_layer_slots, 1), std::max<uint64_t>(plan.total_edge_slots, 1),
+                          sigma_words(), true);
+        vc = c.view(true);
+        vc.n = n;
+        check(pvac_hip_compact_exec(ctx_, &plan, &vx, &vc));
+        return detail::from_device<CipherT>(c, n, plan.total_layer_slots, plan.total_edge_slots, prm_.m_bits, true,
+                                            stream_);
+    }
+
+    // Batched ct_recrypt (ops/recrypt.hpp:26-41) against ek.zero_pool. The reference draws one
+    // csprng_u64 per loop iteration that runs (recrypt.hpp:32), and whether iteration k runs depends
+    // on draws 0..k-1 only. So the draws are taken lazily, level by level: the batch runs with the
+    // words drawn so far; every cipher that wanted one more iteration than it has words for gets one
+    // more word of rnd (cipher order within a level) and only those ciphers run again. A single
+    // cipher therefore consumes rnd exactly as the reference consumes getrandom; a cipher that does
+    // not iterate (a fresh cipher, a fresh product) is done after the first pass. iters_out
+    // (optional) receives the iteration counts.
+    template <class PubKeyT, class CipherT>
+    std::vector<CipherT> ct_recrypt(const PubKeyT& pk, const std::vector<CipherT>& pool,
+                                    const std::vector<const CipherT*>& cs, const RandomSource& rnd,
+                                    std::vector<uint32_t>* iters_out = nullptr) {
+        const size_t n = cs.size();
+        if (!n) return {};
+        ensure_ubk(pk);
+        std::vector<const CipherT*> pp;
+        for (const CipherT& z : pool) pp.push_back(&z);
+        detail::batch p;
+        detail::to_host(pp, sigma_words(), true, p);
+        detail::upload(p, stream_, true);
+        std::vector<CipherT> out(n);
+        std::vector<uint32_t> iters(n, 0), drawn(n, 0);
+        std::vector<uint64_t> picks(8 * n, 0);
+        std::vector<size_t> pending(n);
+        for (size_t i = 0; i < n; ++i) pending[i] = i;
+        while (!pending.empty()) {
+            const size_t m = pending.size();
+            std::vector<const CipherT*> sub(m);
+            std::vector<uint64_t> sub_picks(8 * m);
+            for (size_t j = 0; j < m; ++j) {
+                sub[j] = cs[pending[j]];
+                std::memcpy(&sub_picks[8 * j], &picks[8 * pending[j]], 64);
+            }
+            std::vector<uint32_t> sub_iters(m, 0);
+            std::vector<CipherT> sub_out = recrypt_run<CipherT>(p, sub, sub_picks, sub_iters);
+            std::vector<size_t> next;
+            for (size_t j = 0; j < m; ++j) {
+                const size_t i = pending[j];
+                if (sub_iters[j] > drawn[i]) {   // iteration drawn[i] runs: it needs its word
+                    picks[8 * i + drawn[i]++] = rnd();
+                    next.push_back(i);
+                } else {
+                    out[i] = std::move(sub_out[j]);
+                    iters[i] = sub_iters[j];
+                }
+            }
+            pending.swap(next);
+        }
+        if (iters_out) *iters_out = iters;
+        return out;
+    }
+
 private:
     void check(int rc) {
         if (rc) throw Error(rc, std::string("pvac_hip: ") + pvac_hip_last_error(ctx_));
@@ -840,6 +961,30 @@ private:
         std::vector<uint64_t> f(sk.prf_k.begin(), sk.prf_k.end());
         f.insert(f.end(), sk.lpn_s_bits.begin(), sk.lpn_s_bits.end());
         return f;
+    }
+
+    // one pvac_hip_ct_recrypt_plan + _exec over cs with 8 picks per cipher (p: the uploaded pool)
+    template <class CipherT>
+    std::vector<CipherT> recrypt_run(detail::batch& p, const std::vector<const CipherT*>& cs,
+                                     const std::vector<uint64_t>& picks, std::vector<uint32_t>& iters) {
+        const size_t n = cs.size();
+        detail::batch x, c;
+        detail::to_host(cs, sigma_words(), true, x);
+        detail::upload(x, stream_, true);
+        pvac_ct_batch vx = x.view(true), vp = p.view(true);
+        c.d_l_off.alloc(n); c.d_l_cnt.alloc(n); c.d_e_off.alloc(n); c.d_e_cnt.alloc(n);
+        pvac_ct_batch vc{};
+        vc.l_off = c.d_l_off.p; vc.l_cnt = c.d_l_cnt.p; vc.e_off = c.d_e_off.p; vc.e_cnt = c.d_e_cnt.p;
+        pvac_hip_plan plan{};
+        check(pvac_hip_ct_recrypt_plan(ctx_, &vx, &vp, &vc, &plan));
+        detail::alloc_out(c, n, std::max<uint64_t>(plan.total_layer_slots, 1), std::max<uint64_t>(plan.total_edge_slots, 1),
+                          sigma_words(), true);
+        vc = c.view(true);
+        vc.n = n;
+        iters.assign(n, 0);
+        check(pvac_hip_ct_recrypt_exec(ctx_, &plan, &vx, &vp, picks.data(), &vc, iters.data()));
+        return detail::from_device<CipherT>(c, n, plan.total_layer_slots, plan.total_edge_slots, prm_.m_bits, true,
+                                            stream_);
     }
 
     // one pvac_hip_enc_value launch over (vs, draws) with a fixed stride; status per value
@@ -870,12 +1015,20 @@ private:
     hipStream_t stream_ = nullptr;
     bool h_ready_ = false;
     bool keys_ready_ = false;
+    bool ubk_ready_ = false;
     Phases phases_;
     detail::pinned_batch mul_a_, mul_b_, mul_c_, mul_p_;
     detail::dev_array<uint64_t> mul_nonces_, mul_salts_;
     detail::dev_array<uint32_t> mul_status_;
     std::vector<uint64_t> key_fp_;
 };
+
+namespace detail {
+template <class T, class = void>
+struct has_ubk : std::false_type {};
+template <class T>
+struct has_ubk<T, std::void_t<decltype(std::declval<const T&>().ubk.inv)>> : std::true_type {};
+}  // namespace detail
 
 // Process-wide engines keyed by canon_tag (one public key = one context), device 0 unless
 // PVAC_HIP_DEVICE is set. Contexts are not shared between threads (C ABI contract).
@@ -886,6 +1039,9 @@ Engine& engine_for(const PubKeyT& pk) {
     if (it == engines.end()) {
         const char* d = std::getenv("PVAC_HIP_DEVICE");
         it = engines.emplace(pk.canon_tag, std::make_unique<Engine>(d ? std::atoi(d) : 0, Engine::params_of(pk))).first;
+        // pk.ubk.inv goes up once with the engine (ubk_apply, ct_recrypt); key types without it skip this
+        if constexpr (detail::has_ubk<PubKeyT>::value)
+            if (!pk.ubk.inv.empty()) it->second->ensure_ubk(pk);
     }
     return *it->second;
 }
@@ -1058,6 +1214,41 @@ std::vector<CipherT> ct_add_batch(const PubKeyT& pk, const std::vector<CipherT>&
     return engine_for(pk).ct_add(a, b, negate_b);
 }
 
+// ---- ct_recrypt and its parts (ops/recrypt.hpp, ops/encrypt.hpp:29-104, crypto/matrix.hpp:306-310)
+template <class PubKeyT, class CipherT>
+double sigma_density(const PubKeyT& pk, const CipherT& C) {
+    return engine_for(pk).sigma_density(std::vector<const CipherT*>{&C})[0];
+}
+
+// in place, as the reference's
+template <class PubKeyT, class CipherT>
+void ubk_apply(const PubKeyT& pk, CipherT& C) {
+    if (C.E.empty()) return;
+    C = engine_for(pk).ubk_apply(pk, std::vector<const CipherT*>{&C})[0];
+}
+
+// compact_edges then compact_layers, in place: the reference's ct_recrypt always ends with the two
+// together (recrypt.hpp:38-39); compact_layers alone changes nothing on the result
+template <class PubKeyT, class CipherT>
+void compact_edges(const PubKeyT& pk, CipherT& C) {
+    C = engine_for(pk).compact(std::vector<const CipherT*>{&C})[0];
+}
+
+template <class PubKeyT, class EvalKeyT, class CipherT>
+CipherT ct_recrypt(const PubKeyT& pk, const EvalKeyT& ek, const CipherT& in, const RandomSource& rnd = os_random_u64) {
+    if (ek.zero_pool.empty() || in.E.empty()) return in;   // recrypt.hpp:27
+    return engine_for(pk).ct_recrypt(pk, ek.zero_pool, std::vector<const CipherT*>{&in}, rnd)[0];
+}
+
+template <class PubKeyT, class EvalKeyT, class CipherT>
+std::vector<CipherT> ct_recrypt_batch(const PubKeyT& pk, const EvalKeyT& ek, const std::vector<CipherT>& in,
+                                      const RandomSource& rnd = os_random_u64,
+                                      std::vector<uint32_t>* iters_out = nullptr) {
+    std::vector<const CipherT*> p;
+    for (auto& x : in) p.push_back(&x);
+    return engine_for(pk).ct_recrypt(pk, ek.zero_pool, p, rnd, iters_out);
+}
+
 // ---- encryption / decryption (ops/encrypt.hpp:289, ops/decrypt.hpp:62) --------------------
 template <class CipherT, class PubKeyT, class SecKeyT>
 CipherT enc_value(const PubKeyT& pk, const SecKeyT& sk, uint64_t v, const RandomSource& rnd = os_random_u64) {
@@ -1075,6 +1266,19 @@ CipherT enc_value_depth(const PubKeyT& pk, const SecKeyT& sk, uint64_t v, int de
 template <class CipherT, class PubKeyT, class SecKeyT>
 CipherT enc_zero_depth(const PubKeyT& pk, const SecKeyT& sk, int depth_hint, const RandomSource& rnd = os_random_u64) {
     return enc_value_depth<CipherT>(pk, sk, 0, depth_hint, rnd);
+}
+
+// make_evalkey (ops/recrypt.hpp:12-19): pool_size enc_zero_depth ciphers, then enc_value(1), in the
+// reference's draw order
+template <class EvalKeyT, class PubKeyT, class SecKeyT>
+EvalKeyT make_evalkey(const PubKeyT& pk, const SecKeyT& sk, size_t pool_size, int depth_hint,
+                      const RandomSource& rnd = os_random_u64) {
+    using CipherT = std::decay_t<decltype(std::declval<EvalKeyT&>().enc_one)>;
+    EvalKeyT ek;
+    ek.zero_pool.reserve(pool_size);
+    for (size_t i = 0; i < pool_size; ++i) ek.zero_pool.push_back(enc_zero_depth<CipherT>(pk, sk, depth_hint, rnd));
+    ek.enc_one = enc_value<CipherT>(pk, sk, 1, rnd);
+    return ek;
 }
 
 template <class CipherT, class PubKeyT, class SecKeyT>

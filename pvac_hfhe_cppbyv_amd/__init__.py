@@ -143,6 +143,16 @@ def load_library(path: str = _LIB_PATH) -> C.CDLL:
                                   C.POINTER(CtBatch)], i32),
         "pvac_hip_ct_scale": ([vp, C.POINTER(CtBatch), u64, u64], i32),
         "pvac_hip_sigma_batch": ([vp, C.POINTER(CtBatch), vp], i32),
+        "pvac_hip_ctx_set_ubk": ([vp, vp, u32], i32),
+        "pvac_hip_sigma_popcount": ([vp, C.POINTER(CtBatch), vp], i32),
+        "pvac_hip_ubk_apply": ([vp, C.POINTER(CtBatch), vp], i32),
+        "pvac_hip_compact_plan": ([vp, C.POINTER(CtBatch), C.POINTER(CtBatch), C.POINTER(Plan)], i32),
+        "pvac_hip_compact_exec": ([vp, C.POINTER(Plan), C.POINTER(CtBatch), C.POINTER(CtBatch)], i32),
+        "pvac_hip_compact_path_count": ([vp, C.POINTER(u64)], i32),
+        "pvac_hip_ct_recrypt_plan": ([vp, C.POINTER(CtBatch), C.POINTER(CtBatch), C.POINTER(CtBatch),
+                                      C.POINTER(Plan)], i32),
+        "pvac_hip_ct_recrypt_exec": ([vp, C.POINTER(Plan), C.POINTER(CtBatch), C.POINTER(CtBatch), vp,
+                                      C.POINTER(CtBatch), vp], i32),
         "pvac_hip_gen_fresh_batch": ([vp, u64, u32, C.POINTER(CtBatch)], i32),
         "pvac_hip_gen_fresh_batch_at": ([vp, u64, u64, u32, C.POINTER(CtBatch)], i32),
         "pvac_hip_fill_nonces": ([vp, u64, u64, C.POINTER(CtBatch), C.POINTER(CtBatch), C.POINTER(CtBatch), vp], i32),
@@ -210,8 +220,10 @@ class DeviceBatch:
     def struct(self) -> CtBatch:
         # positional integer addresses (0 = NULL): built on every call, so kept cheap
         p = lambda t: 0 if t is None else t.data_ptr()
+        sg = self.sigma   # (edge slots, words per row): 128 words for the reference's m_bits = 8192
         return CtBatch(self.n, p(self.l_off), p(self.l_cnt), p(self.layers), p(self.e_off), p(self.e_cnt),
-                       p(self.meta), p(self.w_lo), p(self.w_hi), p(self.sigma), 128, 0)
+                       p(self.meta), p(self.w_lo), p(self.w_hi), p(sg),
+                       sg.shape[1] if sg is not None and sg.dim() == 2 else 128, 0)
 
     @staticmethod
     def empty(n, layer_slots, edge_slots, device, sigma=False):
@@ -622,6 +634,93 @@ class Engine:
         sx = X.struct()
         self._check(self.lib.pvac_hip_sigma_batch(self.ctx, C.byref(sx), C.c_void_p(salts.data_ptr())))
         return X
+
+    # ---- ct_recrypt and its parts (ops/recrypt.hpp, ops/encrypt.hpp:29-104, crypto/matrix.hpp:167-188)
+    def set_ubk(self, inv):
+        """pk.ubk.inv: a permutation of [0, m_bits) (host int32)."""
+        a = np.ascontiguousarray(np.asarray(inv, dtype=np.int32).reshape(-1))
+        self._check(self.lib.pvac_hip_ctx_set_ubk(self.ctx, C.c_void_p(a.ctypes.data), len(a)))
+
+    def sigma_popcount(self, X: DeviceBatch):
+        """Set bits over each cipher's sigma rows (device int64 tensor of X.n exact counts)."""
+        out = self.torch.zeros(max(X.n, 1), dtype=self.torch.int64, device=self.device)
+        sx = X.struct()
+        self._check(self.lib.pvac_hip_sigma_popcount(self.ctx, C.byref(sx), C.c_void_p(out.data_ptr())))
+        return out[:X.n]
+
+    def sigma_density(self, X: DeviceBatch):
+        """sigma_density (ops/encrypt.hpp:29-37) per cipher as the reference computes it: the exact
+        popcount over (edges * m_bits) in long double, rounded to double; 0.0 for an empty cipher."""
+        ones = self.sigma_popcount(X).cpu().numpy().view(np.uint64)
+        ne = X.e_cnt.cpu().numpy().view(np.uint64)[:X.n]
+        return np.array([float(np.longdouble(int(o)) / (np.longdouble(int(e)) * np.longdouble(self.params.m_bits)))
+                         if e else 0.0 for o, e in zip(ones, ne)], np.float64)
+
+    def ubk_apply(self, X: DeviceBatch, active=None):
+        """ubk_apply in place on X's sigma rows; active: optional per-cipher mask (0 = leave untouched)."""
+        if active is not None and not isinstance(active, self.torch.Tensor):
+            active = self.torch.from_numpy(np.ascontiguousarray(np.asarray(active, dtype=np.uint32)).view(np.int32))
+        if active is not None:
+            active = active.to(self.device)
+        sx = X.struct()
+        self._check(self.lib.pvac_hip_ubk_apply(self.ctx, C.byref(sx),
+                                                C.c_void_p(active.data_ptr()) if active is not None else None))
+        return X
+
+    def _out_batch(self, n, plan, words):
+        torch = self.torch
+        e = max(plan.total_edge_slots, 1)
+        z = lambda: torch.zeros(max(n, 1), dtype=torch.int64, device=self.device)
+        return DeviceBatch(n, z(), z(), torch.empty((max(plan.total_layer_slots, 1), 5), dtype=torch.int64,
+                                                    device=self.device),
+                           z(), z(), torch.empty(e, dtype=torch.int64, device=self.device),
+                           torch.empty(e, dtype=torch.int64, device=self.device),
+                           torch.empty(e, dtype=torch.int64, device=self.device),
+                           torch.empty((e, words), dtype=torch.int64, device=self.device))
+
+    def compact(self, X: DeviceBatch) -> DeviceBatch:
+        """compact_edges then compact_layers of every cipher (pvac_hip_compact_plan / _exec)."""
+        torch = self.torch
+        z = lambda: torch.zeros(max(X.n, 1), dtype=torch.int64, device=self.device)
+        C_ = DeviceBatch(X.n, z(), z(), None, z(), z(), None, None, None)
+        plan = Plan()
+        sx, sc = X.struct(), C_.struct()
+        self._check(self.lib.pvac_hip_compact_plan(self.ctx, C.byref(sx), C.byref(sc), C.byref(plan)))
+        words = X.sigma.shape[1] if X.sigma is not None else 128
+        O = self._out_batch(X.n, plan, words)
+        O.l_off, O.e_off = C_.l_off, C_.e_off
+        sc = O.struct()
+        self._check(self.lib.pvac_hip_compact_exec(self.ctx, C.byref(plan), C.byref(sx), C.byref(sc)))
+        return O
+
+    def compact_path_counts(self):
+        """Ciphers compacted since the context was created: {small: batched kernel, merge: merge path}."""
+        v = (C.c_uint64 * 2)()
+        self._check(self.lib.pvac_hip_compact_path_count(self.ctx, v))
+        return {"small": int(v[0]), "merge": int(v[1])}
+
+    def ct_recrypt(self, X: DeviceBatch, pool: DeviceBatch, picks):
+        """ct_recrypt (ops/recrypt.hpp:26-41) of every cipher of X against the zero pool. picks: 8 u64
+        per cipher, the csprng_u64 draws of its iterations in order. Returns (DeviceBatch, iteration
+        counts as numpy u32)."""
+        torch = self.torch
+        pk = np.ascontiguousarray(np.asarray(picks, dtype=np.uint64).reshape(-1))
+        if len(pk) != 8 * X.n:
+            raise PvacError("ct_recrypt: picks needs 8 words per cipher")
+        z = lambda: torch.zeros(max(X.n, 1), dtype=torch.int64, device=self.device)
+        C_ = DeviceBatch(X.n, z(), z(), None, z(), z(), None, None, None)
+        plan = Plan()
+        sx, sp, sc = X.struct(), pool.struct(), C_.struct()
+        self._check(self.lib.pvac_hip_ct_recrypt_plan(self.ctx, C.byref(sx), C.byref(sp), C.byref(sc), C.byref(plan)))
+        words = X.sigma.shape[1] if X.sigma is not None else 128
+        O = self._out_batch(X.n, plan, words)
+        O.l_off, O.e_off = C_.l_off, C_.e_off
+        sc = O.struct()
+        iters = np.zeros(max(X.n, 1), np.uint32)
+        self._check(self.lib.pvac_hip_ct_recrypt_exec(self.ctx, C.byref(plan), C.byref(sx), C.byref(sp),
+                                                      C.c_void_p(pk.ctypes.data) if len(pk) else None, C.byref(sc),
+                                                      C.c_void_p(iters.ctypes.data)))
+        return O, iters[:X.n]
 
     def set_H(self, H_dense: np.ndarray):
         H = np.ascontiguousarray(H_dense, np.uint64)

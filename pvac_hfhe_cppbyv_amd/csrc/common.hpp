@@ -239,6 +239,39 @@ hipError_t launch_add_merge(const pvac_ct_batch& A, const pvac_ct_batch& B, pvac
                             const merge_pair_info& info, uint32_t Bm, int negate_b, void* scratch, size_t scratch_bytes,
                             unsigned long long* counters, hipStream_t st);
 
+// ---- ct_recrypt's parts (k_recrypt.hip): sigma popcounts, ubk_apply, batched compact_edges + compact_layers
+// k_compact_small holds one LDS word per cell of a cipher's key space |L| 2B: 56 KiB of cells next to
+// 6 KiB of layer and scan tables stays inside the 64 KiB a workgroup gets without opting in. With
+// B = 337 that is 21 layers (a recrypt result has 18, a fresh product 8). Ciphers above any of the
+// three bounds take launch_add_merge with an empty B.
+constexpr uint32_t kCompactSmallCells = 14336;
+constexpr uint32_t kCompactSmallLayers = 1024;
+constexpr uint32_t kCompactSmallEdges = 1u << 16;
+// ones[i] (device, n u64) = popcount over cipher i's e_cnt[i] rows of ceil(m_bits / 64) words
+hipError_t launch_sigma_popcount(const pvac_ct_batch& X, uint32_t m_bits, int num_cus, unsigned long long* ones,
+                                 hipStream_t st);
+// in place on every row of every cipher with active[i] != 0 (active nullable): out bit j = in bit perm[j]
+size_t ubk_apply_lds_bytes(uint32_t m_bits);
+hipError_t launch_ubk_apply(const pvac_ct_batch& X, const uint32_t* perm, uint32_t m_bits, const uint32_t* active,
+                            int num_cus, hipStream_t st);
+// compact plan: C.l_off / C.e_off <- X's counts (the caller scans them), cls[i] = PAIR_SMALL / PAIR_LARGE,
+// the PAIR_LARGE ids appended to large_ids, stats: n_large, max_keys (cells of the small ones), max_layers
+hipError_t launch_compact_plan(const pvac_ct_batch& X, pvac_ct_batch& C, uint32_t Bm, uint8_t* cls, uint64_t* large_ids,
+                               plan_stats* stats, hipStream_t st);
+// out[8 k] = {id, |L|, |E|, X.e_off, C.e_off, 0, 0, 0} of cipher ids[k]
+hipError_t launch_compact_gather(const pvac_ct_batch& X, const pvac_ct_batch& C, const uint64_t* ids, uint64_t n,
+                                 uint64_t* out, hipStream_t st);
+// every PAIR_SMALL cipher of X -> C (rows, sigma XOR, exact counts); max_cells from the plan
+hipError_t launch_compact_small(const pvac_ct_batch& X, pvac_ct_batch& C, const uint8_t* cls, uint32_t Bm, uint32_t m_bits,
+                                uint32_t max_cells, hipStream_t st);
+// ct_recrypt plumbing: the plan's capacities (C offsets before their scan), verbatim copies of the
+// ciphers ids[0, m) and the counts of a view scattered back to C
+hipError_t launch_recrypt_plan(const pvac_ct_batch& X, uint64_t max_pl, uint64_t max_pe, pvac_ct_batch& C, hipStream_t st);
+hipError_t launch_recrypt_copy(const pvac_ct_batch& X, pvac_ct_batch& C, const uint32_t* ids, uint64_t m, uint32_t m_bits,
+                               hipStream_t st);
+hipError_t launch_scatter_counts(const uint64_t* l_cnt, const uint64_t* e_cnt, const uint32_t* ids, uint64_t m,
+                                 uint64_t* c_l_cnt, uint64_t* c_e_cnt, hipStream_t st);
+
 // ---- ct_mul, general path (k_mul_large.hip and the k_large_* files): multi-kernel, global scratch, one workgroup
 // per (A-layer, B-layer) product task. The host prepares one descriptor per large pair with
 // ABSOLUTE u32-word offsets into one scratch arena (64-bit arrays on even offsets).

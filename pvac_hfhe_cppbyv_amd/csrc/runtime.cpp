@@ -153,6 +153,18 @@ struct pvac_hip_ctx {
     dev_stream_buf<uint64_t> chain_out;      // digests / counts of a chunk before the copy to X's device
     dev_buf<unsigned long long> chain_stats;     // [2 * PVAC_CHAIN_MAX_DEPTH + 1]: edges / products, image pair-steps
     std::vector<int64_t> chain_layout;          // the last call's (streams, chunk, n_devices, ordinals...)
+    // ct_recrypt and its parts (k_recrypt.hip)
+    dev_buf<uint32_t> ubk_perm;              // pk.ubk as a gather: perm[inv[src]] = src (set_ubk)
+    bool have_ubk = false;
+    std::vector<merge_pair_info> compact_host;   // the latest compact plan's ciphers above the LDS bound
+    dev_buf<uint64_t> zero_n;                // zero words: the counts of the merge path's empty B
+    uint64_t compact_path[2] = {};           // ciphers compacted by k_compact_small / by the merge path
+    dev_buf<uint64_t> rc_idx;                // recrypt: per-iteration offset / count views and popcounts
+    dev_buf<uint32_t> rc_ids;                // recrypt: cipher ids of a view
+    struct recrypt_set {                     // recrypt: one of the two intermediate batches
+        dev_buf<pvac_layer> layers;
+        dev_buf<uint64_t> meta, w_lo, w_hi, sigma;
+    } rc_buf[2];
     uint64_t H_gen = 0;                      // bumped whenever H is set (a worker's copy follows it)
     uint64_t H_from = 0;                     // worker: the parent's H_gen its H copy was taken from
 };
@@ -1014,6 +1026,407 @@ int pvac_hip_sigma_batch(pvac_hip_ctx* c, pvac_ct_batch* X, const uint64_t* salt
     if (!c->H.ready) return fail(c, PVAC_EINVAL, "sigma_batch: H not set");
     scoped_timer t(c, "sigma");
     return hip_fail(c, launch_sigma(c->H, c->prm, *X, salts, nullptr, c->num_cus, c->stream), "sigma");
+}
+
+// ---------------------------------------------------------------- ct_recrypt and its parts
+int pvac_hip_ctx_set_ubk(pvac_hip_ctx* c, const int32_t* inv, uint32_t m_bits) {
+    if (!c || !inv) return fail(c, PVAC_EINVAL, "set_ubk: arguments");
+    if (m_bits != c->prm.m_bits) return fail(c, PVAC_EINVAL, "set_ubk: m_bits is not the context's");
+    try {
+        // the kernel gathers: output bit j = input bit perm[j], perm[inv[src]] = src
+        std::vector<uint32_t> perm(m_bits, 0xFFFFFFFFu);
+        for (uint32_t s = 0; s < m_bits; ++s) {
+            const int32_t j = inv[s];
+            if (j < 0 || (uint32_t)j >= m_bits || perm[j] != 0xFFFFFFFFu)
+                return fail(c, PVAC_EINVAL, "set_ubk: inv is not a permutation of [0, m_bits)");
+            perm[j] = s;
+        }
+        hipError_t e = hipStreamSynchronize(c->stream);   // an earlier ubk_apply may still read the table
+        if (e == hipSuccess) e = c->ubk_perm.grow(m_bits, m_bits);
+        if (e == hipSuccess) e = hipMemcpy(c->ubk_perm.get(), perm.data(), (size_t)m_bits * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(c, e, "set_ubk");
+        c->have_ubk = true;
+        return PVAC_OK;
+    } catch (const std::exception& ex) {
+        return fail(c, PVAC_ENOMEM, std::string("set_ubk: ") + ex.what());
+    }
+}
+
+namespace {
+
+bool sigma_ok(const pvac_hip_ctx* c, const pvac_ct_batch* X) {
+    return X->sigma && X->sigma_words >= (c->prm.m_bits + 63) / 64;
+}
+
+// compact's plan: the class of every cipher of X (pair_class), the ciphers above the LDS bound
+// (compact_host, with C's edge offsets) and, with `scan`, C's offsets as the scans of X's counts
+int compact_classify(pvac_hip_ctx* c, const pvac_ct_batch* X, pvac_ct_batch* C, bool scan, pvac_hip_plan* plan) {
+    std::memset(plan, 0, sizeof *plan);
+    plan->kind = 5;
+    plan->n_pairs = X->n;
+    c->compact_host.clear();
+    if (!X->n) return PVAC_OK;
+    if (X->n > 0x7FFFFFFFull) return fail(c, PVAC_ENOSYS, "compact: more than 2^31 - 1 ciphers");
+    const int rc = ensure_pairs(c, X->n);
+    if (rc) return rc;
+    const uint32_t stamp = ++c->plan_stamp;   // earlier plans go stale now (pair_class is shared)
+    pvac_ct_batch Cw = *C;
+    if (!scan) Cw.l_off = Cw.e_off = nullptr;
+    hipError_t e = hipMemsetAsync(c->stats.get(), 0, sizeof(plan_stats), c->stream);
+    if (e == hipSuccess)
+        e = launch_compact_plan(*X, Cw, c->prm.B, c->pair_class.get(), c->large_ids.get(), c->stats.get(), c->stream);
+    if (e == hipSuccess && scan)
+        e = launch_exclusive_scan2_u64(C->l_off, C->e_off, X->n, c->scan_scratch.get(), &c->totals[0], &c->totals[1], c->stream);
+    plan_stats st{};
+    if (e == hipSuccess) e = read_back(c, &st, c->stats.get(), sizeof st);
+    if (e != hipSuccess) return hip_fail(c, e, "compact_plan");
+    plan->total_layer_slots = st.total_layers;
+    plan->total_edge_slots = st.total_edges;
+    plan->max_layers = st.max_layers;
+    plan->max_keys = st.max_keys;
+    plan->n_large = st.n_large;
+    plan->n_small = X->n - st.n_large;
+    if (st.n_large) {
+        std::vector<uint64_t> info(8 * st.n_large);
+        e = launch_compact_gather(*X, *C, c->large_ids.get(), st.n_large, c->large_info.get(), c->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(info.data(), c->large_info.get(), info.size() * 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) return hip_fail(c, e, "compact_plan (merge)");
+        for (uint64_t k = 0; k < st.n_large; ++k) {
+            const uint64_t* o = &info[8 * k];
+            merge_pair_info m{};
+            m.pair = o[0];
+            m.LA = m.L = (uint32_t)o[1];
+            m.nA = o[2];
+            m.nB = 0;
+            m.aeo = o[3];
+            m.beo = 0;
+            m.ceo = o[4];
+            if (o[1] > 30000 || m.nA >= (1ull << 31) || o[1] * c->prm.B * 2 >= 0xFFFFFFFFull) {
+                c->compact_host.clear();
+                return fail(c, PVAC_ENOSYS, "compact_plan: a cipher beyond 30000 layers, 2^31 edges or 2^32 keys");
+            }
+            c->compact_host.push_back(m);
+        }
+        std::sort(c->compact_host.begin(), c->compact_host.end(),
+                  [](const merge_pair_info& x, const merge_pair_info& y) { return x.pair < y.pair; });
+    }
+    plan->reserved[0] = stamp;
+    return PVAC_OK;
+}
+
+int compact_execute(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_ct_batch* X, pvac_ct_batch* C) {
+    if (!X->n) return PVAC_OK;
+    if (plan->reserved[0] != c->plan_stamp || plan->n_large != c->compact_host.size())
+        return fail(c, PVAC_EINVAL, "compact_exec: plan is not this context's latest plan");
+    scoped_timer t(c, "compact");
+    if (plan->n_small) {
+        const int rc = hip_fail(c,
+                                launch_compact_small(*X, *C, c->pair_class.get(), c->prm.B, c->prm.m_bits, plan->max_keys,
+                                                     c->stream),
+                                "compact");
+        if (rc) return rc;
+        c->compact_path[0] += plan->n_small;
+    }
+    if (!plan->n_large) return PVAC_OK;
+    // the merge path of ct_add's guard_budget (k_add_merge.hip), one cipher at a time, with an empty B
+    hipError_t e = c->zero_n.grow(X->n, std::max<size_t>(X->n, 1024));
+    if (e == hipSuccess) e = hipMemsetAsync(c->zero_n.get(), 0, X->n * 8, c->stream);
+    if (e == hipSuccess) e = c->merge_counters.grow(2, 2);
+    if (e != hipSuccess) return hip_fail(c, e, "alloc compact merge");
+    pvac_ct_batch Bz = *X;
+    Bz.l_off = Bz.l_cnt = Bz.e_off = Bz.e_cnt = c->zero_n.get();
+    for (const merge_pair_info& m : c->compact_host) {
+        const size_t need = merge_scratch_bytes(m.nA, m.L);
+        if ((e = c->merge_scratch.grow(need, need)) != hipSuccess) return hip_fail(c, e, "alloc merge scratch");
+        const int rc = hip_fail(c,
+                                launch_add_merge(*X, Bz, *C, m.pair, m, c->prm.B, 0, c->merge_scratch.get(),
+                                                 c->merge_scratch.capacity(), c->merge_counters.get(), c->stream),
+                                "compact merge");
+        if (rc) return rc;
+    }
+    c->compact_path[1] += plan->n_large;
+    return PVAC_OK;
+}
+
+// n words to the device on the context's stream, waited for: the host words may change afterwards
+hipError_t upload_words(pvac_hip_ctx* c, void* dst, const void* src, size_t bytes) {
+    if (!bytes) return hipSuccess;
+    hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    return e;
+}
+
+}  // namespace
+
+int pvac_hip_sigma_popcount(pvac_hip_ctx* c, const pvac_ct_batch* X, uint64_t* ones) {
+    if (!c || !batch_ok(X) || (!ones && X->n)) return fail(c, PVAC_EINVAL, "sigma_popcount: bad arguments");
+    if (!X->n) return PVAC_OK;
+    if (!sigma_ok(c, X)) return fail(c, PVAC_EINVAL, "sigma_popcount: X carries no sigma of m_bits");
+    if (X->n > 0x7FFFFFFFull) return fail(c, PVAC_ENOSYS, "sigma_popcount: more than 2^31 - 1 ciphers");
+    scoped_timer t(c, "sigma_popcount");
+    return hip_fail(c, launch_sigma_popcount(*X, c->prm.m_bits, c->num_cus, (unsigned long long*)ones, c->stream),
+                    "sigma_popcount");
+}
+
+int pvac_hip_ubk_apply(pvac_hip_ctx* c, pvac_ct_batch* X, const uint32_t* active) {
+    if (!c || !batch_ok(X)) return fail(c, PVAC_EINVAL, "ubk_apply: bad arguments");
+    if (!c->have_ubk) return fail(c, PVAC_EINVAL, "ubk_apply: set_ubk first");
+    if (!X->n) return PVAC_OK;
+    if (!sigma_ok(c, X)) return fail(c, PVAC_EINVAL, "ubk_apply: X carries no sigma of m_bits");
+    if (ubk_apply_lds_bytes(c->prm.m_bits) > 64 * 1024) return fail(c, PVAC_ENOSYS, "ubk_apply: m_bits beyond the LDS table");
+    scoped_timer t(c, "ubk_apply");
+    return hip_fail(c, launch_ubk_apply(*X, c->ubk_perm.get(), c->prm.m_bits, active, c->num_cus, c->stream), "ubk_apply");
+}
+
+int pvac_hip_compact_plan(pvac_hip_ctx* c, const pvac_ct_batch* X, pvac_ct_batch* C, pvac_hip_plan* plan) {
+    if (!c || !plan || !batch_ok(X) || !C || (X->n && (!C->l_off || !C->e_off)))
+        return fail(c, PVAC_EINVAL, "compact_plan: bad arguments");
+    if (X->n && !sigma_ok(c, X)) return fail(c, PVAC_EINVAL, "compact_plan: X carries no sigma of m_bits");
+    C->n = X->n;
+    return compact_classify(c, X, C, true, plan);
+}
+
+int pvac_hip_compact_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_ct_batch* X, pvac_ct_batch* C) {
+    if (!c || !plan || plan->kind != 5 || !batch_ok(X) || !batch_ok(C))
+        return fail(c, PVAC_EINVAL, "compact_exec: bad arguments");
+    if (X->n != plan->n_pairs || C->n != plan->n_pairs) return fail(c, PVAC_EINVAL, "compact_exec: plan mismatch");
+    if (!X->n) return PVAC_OK;
+    if (!sigma_ok(c, X) || !sigma_ok(c, C)) return fail(c, PVAC_EINVAL, "compact_exec: X and C must carry sigma of m_bits");
+    if (!C->layers || !C->meta || !C->w_lo || !C->w_hi || C->meta == X->meta || C->sigma == X->sigma ||
+        C->layers == X->layers)
+        return fail(c, PVAC_EINVAL, "compact_exec: C needs row arrays of its own");
+    return compact_execute(c, plan, X, C);
+}
+
+int pvac_hip_compact_path_count(pvac_hip_ctx* c, uint64_t out[2]) {
+    if (!c || !out) return PVAC_EINVAL;
+    out[0] = c->compact_path[0];
+    out[1] = c->compact_path[1];
+    return PVAC_OK;
+}
+
+int pvac_hip_ct_recrypt_plan(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac_ct_batch* pool, pvac_ct_batch* C,
+                             pvac_hip_plan* plan) {
+    if (!c || !plan || !batch_ok(X) || !batch_ok(pool) || !C || (X->n && (!C->l_off || !C->e_off)))
+        return fail(c, PVAC_EINVAL, "ct_recrypt_plan: bad arguments");
+    std::memset(plan, 0, sizeof *plan);
+    plan->kind = 4;
+    plan->n_pairs = X->n;
+    C->n = X->n;
+    if (!X->n) return PVAC_OK;
+    try {
+        int rc = ensure_scan(c, X->n);
+        if (rc) return rc;
+        // the pool is a handful of ciphers: its largest member from a host copy of the counts
+        std::vector<uint64_t> pc(2 * pool->n);
+        hipError_t e = hipSuccess;
+        if (pool->n) {
+            e = hipMemcpyAsync(pc.data(), pool->l_cnt, pool->n * 8, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(pc.data() + pool->n, pool->e_cnt, pool->n * 8, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        }
+        uint64_t max_pl = 0, max_pe = 0;
+        for (uint64_t k = 0; k < pool->n; ++k) {
+            max_pl = std::max(max_pl, pc[k]);
+            max_pe = std::max(max_pe, pc[pool->n + k]);
+        }
+        if (e == hipSuccess) e = launch_recrypt_plan(*X, max_pl, max_pe, *C, c->stream);
+        if (e == hipSuccess)
+            e = launch_exclusive_scan2_u64(C->l_off, C->e_off, X->n, c->scan_scratch.get(), &c->totals[0], &c->totals[1],
+                                           c->stream);
+        unsigned long long tot[2] = {0, 0};
+        if (e == hipSuccess) e = read_back(c, tot, c->totals, sizeof tot);
+        if (e != hipSuccess) return hip_fail(c, e, "ct_recrypt_plan");
+        plan->total_layer_slots = tot[0];
+        plan->total_edge_slots = tot[1];
+        plan->max_layers = (uint32_t)std::min<uint64_t>(max_pl, 0xFFFFFFFFu);
+        plan->max_nb = (uint32_t)std::min<uint64_t>(max_pe, 0xFFFFFFFFu);
+        return PVAC_OK;
+    } catch (const std::exception& ex) {
+        return fail(c, PVAC_ENOMEM, std::string("ct_recrypt_plan: ") + ex.what());
+    }
+}
+
+int pvac_hip_ct_recrypt_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_ct_batch* X, const pvac_ct_batch* pool,
+                             const uint64_t* picks, pvac_ct_batch* C, uint32_t* iters) {
+    if (!c || !plan || plan->kind != 4 || !batch_ok(X) || !batch_ok(pool) || !batch_ok(C))
+        return fail(c, PVAC_EINVAL, "ct_recrypt_exec: bad arguments");
+    const uint64_t n = X->n, pn = pool->n;
+    if (n != plan->n_pairs || C->n != n) return fail(c, PVAC_EINVAL, "ct_recrypt_exec: plan mismatch");
+    if (!n) return PVAC_OK;
+    if (!c->have_ubk) return fail(c, PVAC_EINVAL, "ct_recrypt_exec: set_ubk first");
+    const uint32_t sw = X->sigma_words, m_bits = c->prm.m_bits;
+    if (!sigma_ok(c, X) || !sigma_ok(c, C) || (pn && !sigma_ok(c, pool)))
+        return fail(c, PVAC_EINVAL, "ct_recrypt_exec: X, pool and C must carry sigma of m_bits");
+    if ((sw & 1u) || C->sigma_words != sw || (pn && pool->sigma_words != sw))
+        return fail(c, PVAC_EINVAL, "ct_recrypt_exec: X, pool and C need one even sigma_words");
+    if (!C->layers || !C->meta || !C->w_lo || !C->w_hi || C->meta == X->meta || C->sigma == X->sigma)
+        return fail(c, PVAC_EINVAL, "ct_recrypt_exec: C needs row arrays of its own");
+    if (pn && !picks) return fail(c, PVAC_EINVAL, "ct_recrypt_exec: picks");
+    if (n > 0x7FFFFFFFull) return fail(c, PVAC_ENOSYS, "ct_recrypt_exec: more than 2^31 - 1 ciphers");
+    if (ubk_apply_lds_bytes(m_bits) > 64 * 1024) return fail(c, PVAC_ENOSYS, "ct_recrypt_exec: m_bits beyond the LDS table");
+    try {
+        scoped_timer timer(c, "ct_recrypt");
+        // the shapes of X, of the pool and of C's slots on the host: the loop below is host-driven
+        std::vector<uint64_t> hx(4 * n), hp(4 * pn), hc(2 * n);
+        hipError_t e = hipSuccess;
+        auto down = [&](uint64_t* dst, const uint64_t* src, uint64_t k) {
+            if (e == hipSuccess && k) e = hipMemcpyAsync(dst, src, k * 8, hipMemcpyDeviceToHost, c->stream);
+        };
+        down(&hx[0], X->l_off, n);
+        down(&hx[n], X->l_cnt, n);
+        down(&hx[2 * n], X->e_off, n);
+        down(&hx[3 * n], X->e_cnt, n);
+        down(hp.data(), pool->l_off, pn);
+        down(hp.data() + pn, pool->l_cnt, pn);
+        down(hp.data() + 2 * pn, pool->e_off, pn);
+        down(hp.data() + 3 * pn, pool->e_cnt, pn);
+        down(&hc[0], C->l_off, n);
+        down(&hc[n], C->e_off, n);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        for (uint64_t k = 0; e == hipSuccess && k < pn; ++k)   // C's slots were sized for the plan's pool
+            if (hp[pn + k] > plan->max_layers || hp[3 * pn + k] > plan->max_nb)
+                return fail(c, PVAC_EINVAL, "ct_recrypt_exec: the pool is larger than the planned one");
+        if (e == hipSuccess) e = c->rc_idx.grow(17 * n, 17 * std::max<uint64_t>(n, 64));
+        if (e == hipSuccess) e = c->rc_ids.grow(n, std::max<uint64_t>(n, 64));
+        if (e != hipSuccess) return hip_fail(c, e, "ct_recrypt_exec (shapes)");
+        uint64_t* const R = c->rc_idx.get();
+        auto region = [&](int k) { return R + (uint64_t)k * n; };
+        // the ciphers recrypt returns verbatim (recrypt.hpp:27), and the others: the loop's first view, in X
+        std::vector<uint32_t> ids, cur_id;
+        std::vector<uint64_t> cur[4];
+        for (uint64_t i = 0; i < n; ++i) {
+            if (iters) iters[i] = 0;
+            if (!pn || !hx[3 * n + i]) {
+                ids.push_back((uint32_t)i);
+                continue;
+            }
+            cur_id.push_back((uint32_t)i);
+            for (int f = 0; f < 4; ++f) cur[f].push_back(hx[f * n + i]);
+        }
+        if (!ids.empty()) {
+            e = upload_words(c, c->rc_ids.get(), ids.data(), ids.size() * 4);
+            if (e == hipSuccess) e = launch_recrypt_copy(*X, *C, c->rc_ids.get(), ids.size(), m_bits, c->stream);
+            if (e != hipSuccess) return hip_fail(c, e, "ct_recrypt_exec (copy)");
+        }
+        pvac_ct_batch base = *X;   // the arrays the current view's ciphers live in
+        std::vector<uint64_t> up, ones;
+        for (int it = 0; !cur_id.empty(); ++it) {
+            const uint64_t m = cur_id.size();
+            // the view of the ciphers still in the loop: regions 0..3
+            auto view_up = [&](const std::vector<uint32_t>& sel, int first_region) {
+                for (int f = 0; f < 4 && e == hipSuccess; ++f) {
+                    up.resize(sel.size());
+                    for (size_t k = 0; k < sel.size(); ++k) up[k] = cur[f][sel[k]];
+                    e = upload_words(c, region(first_region + f), up.data(), up.size() * 8);
+                }
+            };
+            auto view_of = [&](const pvac_ct_batch& b, uint64_t count, int first_region) {
+                pvac_ct_batch v = b;
+                v.n = count;
+                v.l_off = region(first_region);
+                v.l_cnt = region(first_region + 1);
+                v.e_off = region(first_region + 2);
+                v.e_cnt = region(first_region + 3);
+                return v;
+            };
+            std::vector<uint32_t> all(m), fin, cont;
+            for (uint64_t k = 0; k < m; ++k) all[k] = (uint32_t)k;
+            if (it < 8) {
+                // sigma_needs_balance (recrypt.hpp:21-24) from the exact popcounts, in the reference's arithmetic
+                view_up(all, 0);
+                const pvac_ct_batch V = view_of(base, m, 0);
+                if (e == hipSuccess)
+                    e = launch_sigma_popcount(V, m_bits, c->num_cus, (unsigned long long*)region(16), c->stream);
+                ones.resize(m);
+                if (e == hipSuccess) e = hipMemcpyAsync(ones.data(), region(16), m * 8, hipMemcpyDeviceToHost, c->stream);
+                if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+                if (e != hipSuccess) return hip_fail(c, e, "ct_recrypt_exec (density)");
+                for (uint64_t k = 0; k < m; ++k) {
+                    const long double total = (long double)cur[3][k] * (long double)m_bits;
+                    const double d = (double)((long double)ones[k] / total);
+                    (d < 0.495 || d > 0.505 ? cont : fin).push_back((uint32_t)k);
+                }
+            } else {
+                fin = all;
+            }
+            if (!fin.empty()) {   // compact_edges + compact_layers into C's slots (recrypt.hpp:38-39)
+                const uint64_t f = fin.size();
+                view_up(fin, 0);
+                std::vector<uint64_t> co(f);
+                std::vector<uint32_t> fid(f);
+                for (uint64_t k = 0; k < f; ++k) {
+                    fid[k] = cur_id[fin[k]];
+                    co[k] = hc[fid[k]];
+                    if (iters) iters[fid[k]] = (uint32_t)it;
+                }
+                if (e == hipSuccess) e = upload_words(c, region(12), co.data(), f * 8);
+                for (uint64_t k = 0; k < f; ++k) co[k] = hc[n + fid[k]];
+                if (e == hipSuccess) e = upload_words(c, region(14), co.data(), f * 8);
+                if (e == hipSuccess) e = upload_words(c, c->rc_ids.get(), fid.data(), f * 4);
+                if (e != hipSuccess) return hip_fail(c, e, "ct_recrypt_exec (compact views)");
+                const pvac_ct_batch Xs = view_of(base, f, 0);
+                pvac_ct_batch Cs = view_of(*C, f, 12);
+                pvac_hip_plan cp;
+                int rc = compact_classify(c, &Xs, &Cs, false, &cp);
+                if (!rc) rc = compact_execute(c, &cp, &Xs, &Cs);
+                if (rc) return rc;
+                e = launch_scatter_counts(region(13), region(15), c->rc_ids.get(), f, C->l_cnt, C->e_cnt, c->stream);
+                if (e != hipSuccess) return hip_fail(c, e, "ct_recrypt_exec (counts)");
+            }
+            if (cont.empty()) break;
+            // ct_add of the picked pool members (recrypt.hpp:32-33), then ubk_apply (:34); ct_add has
+            // applied guard_budget to the same edges, so :35 changes nothing
+            const uint64_t m2 = cont.size();
+            view_up(cont, 0);
+            for (int f = 0; f < 4 && e == hipSuccess; ++f) {
+                up.resize(m2);
+                for (uint64_t k = 0; k < m2; ++k) up[k] = hp[f * pn + picks[8ull * cur_id[cont[k]] + it] % pn];
+                e = upload_words(c, region(4 + f), up.data(), m2 * 8);
+            }
+            if (e != hipSuccess) return hip_fail(c, e, "ct_recrypt_exec (add views)");
+            const pvac_ct_batch Av = view_of(base, m2, 0), Bv = view_of(*pool, m2, 4);
+            pvac_ct_batch Cv{};
+            Cv = view_of(Cv, m2, 8);
+            Cv.sigma_words = sw;
+            pvac_hip_plan ap;
+            int rc = pvac_hip_ct_add_plan(c, &Av, &Bv, &Cv, &ap);
+            if (rc) return rc;
+            auto& buf = c->rc_buf[it & 1];
+            const size_t nl = std::max<uint64_t>(ap.total_layer_slots, 1), ne = std::max<uint64_t>(ap.total_edge_slots, 1);
+            e = buf.layers.grow(nl, nl);
+            if (e == hipSuccess) e = buf.meta.grow(ne, ne);
+            if (e == hipSuccess) e = buf.w_lo.grow(ne, ne);
+            if (e == hipSuccess) e = buf.w_hi.grow(ne, ne);
+            if (e == hipSuccess) e = buf.sigma.grow(ne * sw, ne * sw);
+            if (e != hipSuccess) return hip_fail(c, e, "ct_recrypt_exec (alloc)");
+            Cv.layers = buf.layers.get();
+            Cv.meta = buf.meta.get();
+            Cv.w_lo = buf.w_lo.get();
+            Cv.w_hi = buf.w_hi.get();
+            Cv.sigma = buf.sigma.get();
+            rc = pvac_hip_ct_add_exec(c, &ap, &Av, &Bv, 0, &Cv);
+            if (rc) return rc;
+            e = launch_ubk_apply(Cv, c->ubk_perm.get(), m_bits, nullptr, c->num_cus, c->stream);
+            // the next view: the sums, where ct_add put them
+            std::vector<uint32_t> next_id(m2);
+            for (uint64_t k = 0; k < m2; ++k) next_id[k] = cur_id[cont[k]];
+            for (int f = 0; f < 4; ++f) {
+                cur[f].assign(m2, 0);
+                down(cur[f].data(), region(8 + f), m2);
+            }
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) return hip_fail(c, e, "ct_recrypt_exec (step)");
+            cur_id.swap(next_id);
+            base = Cv;
+        }
+        return PVAC_OK;
+    } catch (const std::exception& ex) {
+        return fail(c, PVAC_ENOMEM, std::string("ct_recrypt_exec: ") + ex.what());
+    }
 }
 
 // ---------------------------------------------------------------- LPN PRF
