@@ -215,11 +215,26 @@ int pvac_hip_ct_mul_status(pvac_hip_ctx* ctx, uint32_t* out, size_t n);
  * gsum(X, l) = sum of +/- w * powg_B[idx] over X's edges in layer l (metrics.hpp:70-86). C is a
  * ct_mul_exec output of (A, B) with `nonces`: a product layer is identified by the nonce it
  * carries (compact_layers renumbers C's layers); a dropped product layer must have a zero product.
+ * A C layer with edges must carry the nonce of exactly one product slot and have rule 1 (PROD);
+ * edges whose layer_id is outside their cipher's layers are ignored, as by the reference's loops.
  * Needs pvac_hip_ctx_set_powg. status (nullable, DEVICE, n u32): 0 holds, 1 violated, 2 an edge
- * idx >= B, 3 a cipher of more than 2^21 edges (not checked). *n_bad (host) = pairs with status != 0.
- * Synchronous. */
+ * of A, B or C with idx >= B, 3 a cipher of 2^21 edges or more (not checked: the per-layer sums are
+ * taken over 43/42/42-bit limbs in u64: n terms of at most 2^43 - 1 stay below 2^64 up to n = 2^21
+ * and can pass it from 2^21 + 1, and the check refuses from 2^21 on; 3 wins over 2, 2 over 1).
+ * *n_bad (host) = pairs with status != 0. Synchronous.
+ * Tables: per pair the check keeps seven arrays, each rounded up to 16 bytes: 16 B bytes of powg
+ * words; 48 |A.L|, 48 |B.L| and 48 |C.L| bytes of layer sums; 4 |C.L| bytes of edge counts; 16 and
+ * 4 bytes per product slot (|A.L||B.L| slots). With the batch's maxima of |A.L|, |B.L|, |C.L| and
+ * |A.L||B.L| (each taken on its own) their total decides the mode of the whole call: up to 163,824
+ * bytes (a workgroup's 160 KiB of LDS less 16 bytes of the kernel's own state) the tables live in
+ * LDS, one workgroup per pair over min(n, 8 x CU count) workgroups; above, in per-workgroup slabs
+ * of global scratch over min(n, 2 x CU count) workgroups. Both modes compute the same statuses. */
 int pvac_hip_check_mul_gsum(pvac_hip_ctx* ctx, const pvac_ct_batch* A, const pvac_ct_batch* B, const pvac_ct_batch* C,
                             const uint64_t* nonces, uint32_t* status, uint64_t* n_bad);
+/* pvac_hip_check_mul_gsum calls on this context since it was created (diagnostics and tests) that
+ * ran to completion with n > 0: out[0] with the tables in LDS, out[1] in global slabs. The checks
+ * of pvac_hip_ct_mul_chain run on its workers' contexts and are not counted here. */
+int pvac_hip_check_mul_gsum_path_count(pvac_hip_ctx* ctx, uint64_t out[2]);
 
 /* ---------------------------------------------------------------- depth chains
  * c_0 = X[i], c_k = ct_mul(c_{k-1}, X[i]) for k = 1..depth, for every input i of X: the reference's

@@ -137,6 +137,7 @@ def load_library(path: str = _LIB_PATH) -> C.CDLL:
         "pvac_hip_issue_probe": ([vp, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double)], i32),
         "pvac_hip_check_mul_gsum": ([vp, C.POINTER(CtBatch), C.POINTER(CtBatch), C.POINTER(CtBatch), vp, vp,
                                      C.POINTER(u64)], i32),
+        "pvac_hip_check_mul_gsum_path_count": ([vp, C.POINTER(u64)], i32),
         "pvac_hip_ct_add_plan": ([vp, C.POINTER(CtBatch), C.POINTER(CtBatch), C.POINTER(CtBatch),
                                   C.POINTER(Plan)], i32),
         "pvac_hip_ct_add_exec": ([vp, C.POINTER(Plan), C.POINTER(CtBatch), C.POINTER(CtBatch), i32,
@@ -589,6 +590,13 @@ class Engine:
         if status:
             return bad.value, st.cpu().numpy().view(np.uint32)[:A.n]
         return bad.value
+
+    def check_mul_gsum_path_counts(self):
+        """check_mul_gsum calls on this context since it was created: {lds: layer tables in LDS,
+        slab: in global slabs} (include/pvac_hip.h gives the switch in terms of the table sizes)."""
+        v = (C.c_uint64 * 2)()
+        self._check(self.lib.pvac_hip_check_mul_gsum_path_count(self.ctx, v))
+        return {"lds": int(v[0]), "slab": int(v[1])}
 
     def ct_add(self, A: DeviceBatch, B: DeviceBatch, negate=False, sigma=False):
         torch = self.torch

@@ -18,7 +18,9 @@
 // LDS u64 atomics (< 2^21 edges per cipher), then folded and P - M taken once. Equal to the
 // reference's fp_add / fp_sub chains, which compute exact residues for canonical terms.
 // Status per pair: 0 holds, 1 violated, 2 an edge idx >= B (the reference reads past powg_B),
-// 3 too many edges (> 2^21 in one cipher: the limb sums could overflow; not checked).
+// 3 too many edges (>= 2^21 in one cipher; not checked). The bound: a limb is at most 2^43 - 1, so a
+// (layer, channel) sum of n terms is at most n (2^43 - 1): 2^64 - 2^21 at n = 2^21, past 2^64 from
+// n = 2^21 + 1. The kernel tests e_cnt >> 21 and so refuses from n = 2^21 on, one count early.
 #include <algorithm>
 
 #include "common.hpp"
@@ -214,7 +216,9 @@ hipError_t launch_check_sizes(const pvac_ct_batch& A, const pvac_ct_batch& B, co
 }
 
 namespace {
-constexpr uint32_t kCheckLds = 160u * 1024u;
+// a workgroup's 160 KiB of LDS less the 16 bytes that k_check_gsum's own `bad` word takes in front of
+// the 16-byte aligned tables (tables of exactly 160 KiB would not launch)
+constexpr uint32_t kCheckLds = 160u * 1024u - 16u;
 uint64_t check_blocks(uint64_t n, int num_cus, bool global) {
     const uint64_t b = (uint64_t)num_cus * (global ? 2 : 8);
     return b > n ? n : b;

@@ -159,6 +159,7 @@ struct pvac_hip_ctx {
     std::vector<merge_pair_info> compact_host;   // the latest compact plan's ciphers above the LDS bound
     dev_buf<uint64_t> zero_n;                // zero words: the counts of the merge path's empty B
     uint64_t compact_path[2] = {};           // ciphers compacted by k_compact_small / by the merge path
+    uint64_t check_path[2] = {};             // check_mul_gsum calls with the tables in LDS / in global slabs
     dev_buf<uint64_t> rc_idx;                // recrypt: per-iteration offset / count views and popcounts
     dev_buf<uint32_t> rc_ids;                // recrypt: cipher ids of a view
     struct recrypt_set {                     // recrypt: one of the two intermediate batches
@@ -1690,7 +1691,15 @@ int pvac_hip_check_mul_gsum(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_
     if (e == hipSuccess) e = hipMemcpyAsync(&bad, cnt, sizeof bad, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return hip_fail(c, e, "check_mul_gsum");
+    c->check_path[gs ? 1 : 0]++;
     *n_bad = bad;
+    return PVAC_OK;
+}
+
+int pvac_hip_check_mul_gsum_path_count(pvac_hip_ctx* c, uint64_t out[2]) {
+    if (!c || !out) return PVAC_EINVAL;
+    out[0] = c->check_path[0];
+    out[1] = c->check_path[1];
     return PVAC_OK;
 }
 

@@ -12,9 +12,10 @@ from helpers import Cipher, default_params, fixture_secret, pack_device_batch, r
 pytestmark = pytest.mark.gpu
 
 
-def _stepwise(eng, X, depth, seed, chunk):
+def _stepwise(eng, X, depth, seed, chunk, on_step=None):
     """The same chains step by step on the caller's stream, chunk by chunk with the library's nonce
-    seeds (nonce_seed + 97 * first_input + step): final digests, counts and per-step edge sums."""
+    seeds (nonce_seed + 97 * first_input + step): final digests, counts and per-step edge sums.
+    on_step(first_input, step, A, X, C, nonces) sees every step's device batches."""
     import torch
     from pvac_hfhe_cppbyv_amd import DeviceBatch
     dig, cnt, edges = [], [], [0] * depth
@@ -27,7 +28,9 @@ def _stepwise(eng, X, depth, seed, chunk):
             Cb, plan = eng.ct_mul_plan(cur, Xv)
             nonces = torch.empty(2 * max(plan.total_layer_slots, 1), dtype=torch.int64, device=eng.device)
             eng.fill_random(nonces, seed + 97 * c0 + d)
-            cur = eng.ct_mul(cur, Xv, nonces=nonces, C_=Cb, plan=plan)
+            prev, cur = cur, eng.ct_mul(cur, Xv, nonces=nonces, C_=Cb, plan=plan)
+            if on_step:
+                on_step(c0, d, prev, Xv, cur, nonces)
             edges[d] += int(cur.e_cnt[:k].sum().item())
         dig.append(eng.digest(cur).cpu().numpy().view(np.uint64).copy())
         cnt.append(cur.e_cnt[:k].cpu().numpy().view(np.uint64).copy())
@@ -667,3 +670,38 @@ def test_chain_image_redo_of_mixed_sizes(oracle):
     oracle.lib.orc_ct_mul_chain_ops_timed(ctypes.byref(default_params(tag, edge_budget=budget)), n, *(P_(a) for a in px),
                                           depth, 1, *(P_(a) for a in po), 4, P_(ocnt), P_(odig), P_(se))
     assert np.array_equal(ocnt, img2["counts"]) and np.array_equal(odig, img2["digests"])
+
+
+def test_chain_reports_gsum_failures(oracle):
+    """A gsum violation inside a chain worker reaches stats.gsum_failed: with a powg table of an
+    element g with g^B != 1 (index sums that wrap mod B break the invariant) the call reports exactly
+    the pair-steps that the CPU model (gsum_model.py) flags on the step-by-step host copies; with the
+    key's table, none."""
+    from gsum_cases import powg_from
+    from gsum_model import status
+    from pvac_hfhe_cppbyv_amd import Engine
+    eng = Engine(device=0, canon_tag=fixture_secret()[1]["canon_tag"])
+    n, depth, chunk, seed = 12, 2, 5, 0x6E
+    X, man = _enc_inputs(eng, n, 0x6E5)
+    good = read_u64("powg_B.u64")
+    wrong = powg_from(3, 337)
+    assert pow(3, 337, 2**127 - 1) != 1
+    flagged = {"good": 0, "wrong": 0}
+
+    def on_step(c0, d, A, Xv, C_, nonces):
+        nz = nonces.cpu().numpy().view(np.uint64)
+        lo = C_.l_off.cpu().numpy().view(np.uint64)
+        for i, (a, x, c) in enumerate(zip(A.to_host(), Xv.to_host(), C_.to_host())):
+            s = 2 * (int(lo[i]) + a.nL + x.nL)
+            t = [Cipher(v.layers, v.meta, v.w_lo, v.w_hi) for v in (a, x, c)]
+            for name, powg in (("good", good), ("wrong", wrong)):
+                flagged[name] += status(oracle, *t, nz[s:s + 2 * a.nL * x.nL], powg, 337) != 0
+
+    _stepwise(eng, X, depth, seed, chunk, on_step)
+    assert flagged["good"] == 0 and flagged["wrong"] >= n * depth - 2   # all or nearly all; never vacuous
+    eng.set_powg(wrong)
+    r = eng.ct_mul_chain(X, depth, nonce_seed=seed, streams=2, chunk=chunk, check_gsum=True)
+    assert r["gsum_pairs"] == depth * n and r["gsum_failed"] == flagged["wrong"]
+    eng.set_powg(good)
+    r = eng.ct_mul_chain(X, depth, nonce_seed=seed, streams=2, chunk=chunk, check_gsum=True)
+    assert r["gsum_pairs"] == depth * n and r["gsum_failed"] == 0
