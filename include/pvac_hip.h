@@ -423,6 +423,21 @@ int pvac_hip_ct_recrypt_plan(pvac_hip_ctx* ctx, const pvac_ct_batch* X, const pv
 int pvac_hip_ct_recrypt_exec(pvac_hip_ctx* ctx, const pvac_hip_plan* plan, const pvac_ct_batch* X,
                              const pvac_ct_batch* pool, const uint64_t* picks, pvac_ct_batch* C, uint32_t* iters);
 
+/* ---------------------------------------------------------------- commitments
+ * commit_ct (ops/commit.hpp:12-88) of every cipher of X: digests[32 i ..] (DEVICE, 32 * X->n bytes) =
+ * SHA-256("pvac.dom.commit" | H_digest | le64 canon_tag | layers | edges), a layer as u8 rule then
+ * le64 ztag, nonce_lo, nonce_hi (BASE) or le64 pa, pb (any other rule), an edge as le64 layer_id,
+ * le64 idx, u8 ch, le64 w_lo, le64 (w_hi & 2^63 - 1) and, when X->sigma is set, the first
+ * (m_bits + 7) / 8 bytes of its sigma row (row stride X->sigma_words). X->sigma == NULL hashes no
+ * sigma bytes: the commitment of the same ciphers with every edge's nbits = 0 (the fixtures'
+ * "commit_weights"). H_digest is the context's (gen_H, set_H or set_H_digest; PVAC_EINVAL while it
+ * is unknown) and canon_tag its params'; sigma_words * 64 < m_bits is PVAC_EINVAL. Capacity-padded
+ * CSR (a ct_mul_exec output), empty ciphers and n = 0 are fine. One cipher per lane, the ciphers
+ * dealt to lanes from a counter, so a ragged batch costs no more than its share of the work; one
+ * very large cipher is a serial chain of its 64-byte blocks. Enqueued on the
+ * context's stream; not synchronous. */
+int pvac_hip_commit_ct(pvac_hip_ctx* ctx, const pvac_ct_batch* X, uint8_t* digests);
+
 /* ---------------------------------------------------------------- synthetic inputs / checks
  * Fresh-shaped cipher generator used by bench.py (SURVEY §8(d) cfg 3 generator): per cipher
  * 2 BASE layers (random ztag/nonce), per layer `edges_per_layer` distinct (idx, ch), uniform

@@ -35,6 +35,7 @@
 #include <sys/random.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <condition_variable>
 #include <exception>
@@ -951,6 +952,44 @@ public:
         return out;
     }
 
+    // commit_ct (ops/commit.hpp:12-88) per cipher under pk.H_digest and pk.canon_tag. The reference
+    // hashes each edge's own e.s.nbits; a cipher here has every edge at nbits = 0 (weights only) or
+    // every edge at pk.prm.m_bits, and a batch may mix the two kinds (one ABI call per kind). Any
+    // other width throws: there is no host fallback.
+    template <class PubKeyT, class CipherT>
+    std::vector<std::array<uint8_t, 32>> commit_ct(const PubKeyT& pk, const std::vector<const CipherT*>& cs) {
+        const size_t n = cs.size();
+        std::vector<std::array<uint8_t, 32>> out(n);
+        if (!n) return out;
+        check(pvac_hip_ctx_set_H_digest(ctx_, pk.H_digest.data()));
+        std::vector<size_t> ids[2];   // [0] weights only, [1] with sigma
+        for (size_t i = 0; i < n; ++i) {
+            const size_t nb = cs[i]->E.empty() ? 0 : cs[i]->E[0].s.nbits;
+            for (const auto& e : cs[i]->E)
+                if (e.s.nbits != nb) throw Error(PVAC_EINVAL, "commit_ct: a cipher's edges disagree on sigma nbits");
+            if (nb != 0 && nb != (size_t)prm_.m_bits)
+                throw Error(PVAC_EINVAL, "commit_ct: sigma nbits is neither 0 nor pk.prm.m_bits");
+            ids[nb != 0].push_back(i);
+        }
+        for (int kind = 0; kind < 2; ++kind) {
+            const size_t m = ids[kind].size();
+            if (!m) continue;
+            std::vector<const CipherT*> sub(m);
+            for (size_t j = 0; j < m; ++j) sub[j] = cs[ids[kind][j]];
+            detail::batch x;
+            detail::to_host(sub, sigma_words(), kind == 1, x);
+            detail::upload(x, stream_, kind == 1);
+            pvac_ct_batch vx = x.view(kind == 1);
+            detail::dev_array<uint8_t> dig(32 * m);
+            check(pvac_hip_commit_ct(ctx_, &vx, dig.p));
+            std::vector<uint8_t> h(32 * m);
+            dig.download(h.data(), h.size(), stream_);
+            detail::hip_ok(hipStreamSynchronize(stream_), "sync");
+            for (size_t j = 0; j < m; ++j) std::memcpy(out[ids[kind][j]].data(), &h[32 * j], 32);
+        }
+        return out;
+    }
+
 private:
     void check(int rc) {
         if (rc) throw Error(rc, std::string("pvac_hip: ") + pvac_hip_last_error(ctx_));
@@ -1247,6 +1286,20 @@ std::vector<CipherT> ct_recrypt_batch(const PubKeyT& pk, const EvalKeyT& ek, con
     std::vector<const CipherT*> p;
     for (auto& x : in) p.push_back(&x);
     return engine_for(pk).ct_recrypt(pk, ek.zero_pool, p, rnd, iters_out);
+}
+
+// ---- commit_ct (ops/commit.hpp:12-88) --------------------------------------------------------
+template <class PubKeyT, class CipherT>
+std::array<uint8_t, 32> commit_ct(const PubKeyT& pk, const CipherT& C) {
+    return engine_for(pk).commit_ct(pk, std::vector<const CipherT*>{&C})[0];
+}
+
+// every cipher's commitment; ciphers with sigma (nbits = pk.prm.m_bits) and without (nbits = 0) may mix
+template <class PubKeyT, class CipherT>
+std::vector<std::array<uint8_t, 32>> commit_ct_batch(const PubKeyT& pk, const std::vector<CipherT>& cs) {
+    std::vector<const CipherT*> p;
+    for (auto& x : cs) p.push_back(&x);
+    return engine_for(pk).commit_ct(pk, p);
 }
 
 // ---- encryption / decryption (ops/encrypt.hpp:289, ops/decrypt.hpp:62) --------------------

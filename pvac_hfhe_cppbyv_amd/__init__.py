@@ -160,6 +160,7 @@ def load_library(path: str = _LIB_PATH) -> C.CDLL:
         "pvac_hip_fill_random": ([vp, u64, vp, C.c_size_t], i32),
         "pvac_hip_batch_digest": ([vp, C.POINTER(CtBatch), vp], i32),
         "pvac_hip_batch_sumdigest": ([vp, C.POINTER(CtBatch), vp], i32),
+        "pvac_hip_commit_ct": ([vp, C.POINTER(CtBatch), vp], i32),
         "pvac_hip_batch_pack": ([vp, C.POINTER(CtBatch), C.POINTER(CtBatch), C.POINTER(u64)], i32),
         "pvac_hip_bucket_count": ([u64], u64),
         "pvac_hip_chain_partition": ([u64, u64, u32, vp], i32),
@@ -771,6 +772,17 @@ class Engine:
         sx = X.struct()
         self._check(self.lib.pvac_hip_batch_sumdigest(self.ctx, C.byref(sx), C.c_void_p(out.data_ptr())))
         return out[:X.n]
+
+    def commit_ct(self, X: DeviceBatch, with_sigma=True):
+        """commit_ct (ops/commit.hpp:12-88) of every cipher of X: an (n, 32) uint8 array of SHA-256
+        digests under the context's H_digest and canon_tag. with_sigma=False (or a batch without
+        sigma) hashes no sigma bytes: the commitment of the same ciphers with every nbits = 0."""
+        out = self.torch.empty((max(X.n, 1), 32), dtype=self.torch.uint8, device=self.device)
+        sx = X.struct()
+        if not with_sigma:
+            sx.sigma = None
+        self._check(self.lib.pvac_hip_commit_ct(self.ctx, C.byref(sx), C.c_void_p(out.data_ptr())))
+        return out[:X.n].cpu().numpy()
 
     def pack(self, X: DeviceBatch) -> DeviceBatch:
         """X's used rows back to back (pvac_hip_batch_pack): dense offsets, arrays of exactly the

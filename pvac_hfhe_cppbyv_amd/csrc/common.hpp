@@ -272,6 +272,12 @@ hipError_t launch_recrypt_copy(const pvac_ct_batch& X, pvac_ct_batch& C, const u
 hipError_t launch_scatter_counts(const uint64_t* l_cnt, const uint64_t* e_cnt, const uint32_t* ids, uint64_t m,
                                  uint64_t* c_l_cnt, uint64_t* c_e_cnt, hipStream_t st);
 
+// ---- commit_ct (k_commit.hip): out[32 i ..] = SHA-256 of cipher i's commit message (commit_msg.hpp).
+// head: commit_head_words (14 words); sigma_bytes: bytes of every edge's sigma row that are hashed, 0 =
+// weights only; counter: one device u64 the launch zeroes (the lanes draw cipher indices from it)
+hipError_t launch_commit_ct(const pvac_ct_batch& X, const uint32_t head[14], uint32_t sigma_bytes, int num_cus,
+                            unsigned long long* counter, uint8_t* out, hipStream_t st);
+
 // ---- ct_mul, general path (k_mul_large.hip and the k_large_* files): multi-kernel, global scratch, one workgroup
 // per (A-layer, B-layer) product task. The host prepares one descriptor per large pair with
 // ABSOLUTE u32-word offsets into one scratch arena (64-bit arrays on even offsets).

@@ -18,6 +18,7 @@
 #include <thread>
 #include <vector>
 
+#include "commit_msg.hpp"
 #include "common.hpp"
 #include "dev_mem.hpp"
 #include "large_plan.hpp"
@@ -166,6 +167,7 @@ struct pvac_hip_ctx {
         dev_buf<pvac_layer> layers;
         dev_buf<uint64_t> meta, w_lo, w_hi, sigma;
     } rc_buf[2];
+    dev_buf<unsigned long long> commit_counter;   // commit_ct: the cipher index its lanes draw from
     uint64_t H_gen = 0;                      // bumped whenever H is set (a worker's copy follows it)
     uint64_t H_from = 0;                     // worker: the parent's H_gen its H copy was taken from
 };
@@ -1768,6 +1770,22 @@ uint64_t pvac_hip_bucket_count(uint64_t n) { return bucket_count_after_reserve(n
 int pvac_hip_batch_digest(pvac_hip_ctx* c, const pvac_ct_batch* X, uint64_t* out) {
     if (!c || !batch_ok(X) || (X->n && !out)) return PVAC_EINVAL;
     return hip_fail(c, launch_batch_digest(*X, out, c->stream), "batch_digest");
+}
+
+int pvac_hip_commit_ct(pvac_hip_ctx* c, const pvac_ct_batch* X, uint8_t* digests) {
+    if (!c || !batch_ok(X) || (X->n && !digests)) return fail(c, PVAC_EINVAL, "commit_ct: bad arguments");
+    if (!c->have_digest) return fail(c, PVAC_EINVAL, "commit_ct: H_digest unknown (gen_H, set_H or set_H_digest)");
+    if (X->sigma && (uint64_t)X->sigma_words * 64 < c->prm.m_bits)
+        return fail(c, PVAC_EINVAL, "commit_ct: sigma rows of " + std::to_string(X->sigma_words) + " words are shorter than m_bits");
+    if (!X->n) return PVAC_OK;
+    if (!X->layers || !X->meta || !X->w_lo || !X->w_hi) return fail(c, PVAC_EINVAL, "commit_ct: null row arrays");
+    if (const hipError_t e = c->commit_counter.grow(1, 1)) return hip_fail(c, e, "alloc commit counter");
+    uint32_t head[kCommitHeadWords];
+    commit_head_words(c->H_digest, c->prm.canon_tag, head);
+    const uint32_t sigma_bytes = X->sigma ? (c->prm.m_bits + 7) / 8 : 0;
+    scoped_timer t(c, "commit_ct");
+    return hip_fail(c, launch_commit_ct(*X, head, sigma_bytes, c->num_cus, c->commit_counter.get(), digests, c->stream),
+                    "commit_ct");
 }
 
 int pvac_hip_batch_sumdigest(pvac_hip_ctx* c, const pvac_ct_batch* X, uint64_t* out) {
