@@ -1,0 +1,298 @@
+// rt_keys.cpp — what hangs on the keys: H and its digest, sigma_batch, the secret key and the LPN
+// PRF, enc_value, base_R and dec_value.
+#include <cmath>
+
+#include "ctx.hpp"
+#include "sha256.hpp"
+
+using namespace pvhip;
+
+extern "C" {
+
+// ---------------------------------------------------------------- sigma / H
+int pvac_hip_ctx_set_H(pvac_hip_ctx* c, const uint64_t* H, uint32_t n_cols, uint32_t wpc) try {
+    if (!c || !H) return PVAC_EINVAL;
+    if (n_cols != c->prm.n_bits || wpc != (c->prm.m_bits + 63) / 64) return fail(c, PVAC_EINVAL, "set_H: shape");
+    const int rc = hip_fail(c, sigma_tables_from_dense(c->H, c->prm, H, c->stream), "set_H");
+    if (rc) return rc;
+    ++c->H_gen;
+    // H_digest = SHA-256("H|v2" || le64 m || le64 n || le64 wt || column bytes) (matrix.hpp:218-250)
+    const size_t colbytes = (c->prm.m_bits + 7) / 8;
+    std::vector<uint8_t> msg(28 + (size_t)n_cols * colbytes);
+    std::memcpy(msg.data(), "H|v2", 4);
+    const uint64_t hdr[3] = {c->prm.m_bits, c->prm.n_bits, c->prm.h_col_wt};
+    for (int k = 0; k < 3; ++k)
+        for (int i = 0; i < 8; ++i) msg[4 + 8 * k + i] = (uint8_t)(hdr[k] >> (8 * i));
+    for (uint32_t col = 0; col < n_cols; ++col)
+        for (size_t b = 0; b < colbytes; ++b)
+            msg[28 + (size_t)col * colbytes + b] = (uint8_t)(H[(size_t)col * wpc + b / 8] >> (8 * (b % 8)));
+    sha256_host(msg.data(), msg.size(), c->H_digest);
+    c->have_digest = true;
+    return PVAC_OK;
+} catch (...) { return caught(c, "set_H"); }
+
+int pvac_hip_ctx_gen_H(pvac_hip_ctx* c, uint8_t digest[32]) try {
+    if (!c) return PVAC_EINVAL;
+    scoped_timer t(c, "gen_H");
+    uint8_t d[32];
+    const int rc = hip_fail(c, sigma_tables_generate(c->H, c->prm, d, c->stream), "gen_H");
+    if (rc) return rc;
+    ++c->H_gen;
+    std::memcpy(c->H_digest, d, 32);
+    c->have_digest = true;
+    if (digest) std::memcpy(digest, d, 32);
+    return PVAC_OK;
+} catch (...) { return caught(c, "gen_H"); }
+
+int pvac_hip_sigma_batch(pvac_hip_ctx* c, pvac_ct_batch* X, const uint64_t* salts) try {
+    if (!c || !batch_ok(X) || !salts || !X->sigma) return PVAC_EINVAL;
+    if (!c->H.ready) return fail(c, PVAC_EINVAL, "sigma_batch: H not set");
+    scoped_timer t(c, "sigma");
+    return hip_fail(c, launch_sigma(c->H, c->prm, *X, salts, nullptr, c->num_cus, c->stream), "sigma");
+} catch (...) { return caught(c, "sigma_batch"); }
+
+// ---------------------------------------------------------------- LPN PRF
+int pvac_hip_ctx_set_secret(pvac_hip_ctx* c, const uint64_t prf_k[4], const uint64_t* lpn_s_host, uint32_t lpn_n,
+                            uint32_t lpn_t, uint32_t tau_num, uint32_t tau_den) try {
+    if (!c || !prf_k || !lpn_s_host) return fail(c, PVAC_EINVAL, "set_secret: arguments");
+    const uint32_t words = (lpn_n + 63) / 64;
+    if (lpn_n == 0 || words > 64 || tau_den == 0 || tau_num > tau_den)
+        return fail(c, PVAC_EINVAL, "set_secret: lpn_n must be in [1, 4096], 0 <= tau_num <= tau_den, tau_den > 0");
+    if (lpn_t < 127) return fail(c, PVAC_ENOSYS, "set_secret: lpn_t < 127 not supported");
+    c->prf.lpn_s.release();
+    c->prf.have_secret = false;
+    hipError_t e = c->prf.lpn_s.grow(64, 64);
+    if (e == hipSuccess) e = hipMemset(c->prf.lpn_s.get(), 0, 64 * 8);
+    if (e == hipSuccess) e = hipMemcpy(c->prf.lpn_s.get(), lpn_s_host, (size_t)words * 8, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(c, e, "set_secret");
+    std::memcpy(c->prf.k, prf_k, 32);
+    c->prf.lpn_words = words;
+    c->prf.lpn_t = lpn_t;
+    c->prf.tau_num = tau_num;
+    c->prf.tau_den = tau_den;
+    c->prf.have_secret = true;
+    return PVAC_OK;
+} catch (...) { return caught(c, "set_secret"); }
+
+int pvac_hip_ctx_set_H_digest(pvac_hip_ctx* c, const uint8_t digest[32]) {
+    if (!c || !digest) return PVAC_EINVAL;
+    std::memcpy(c->H_digest, digest, 32);
+    c->have_digest = true;
+    return PVAC_OK;
+}
+
+namespace {
+
+uint64_t fnv1a(const char* d) {   // lpn.hpp:150-157
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (const char* p = d; *p; ++p) { h ^= (uint8_t)*p; h *= 0x100000001b3ull; }
+    return h;
+}
+
+// constants of the key derivation (lpn.hpp:159-186); the first message block is fixed per key
+int prf_setup(pvac_hip_ctx* c, prf_consts& k) {
+    if (!c->prf.have_secret) return fail(c, PVAC_EINVAL, "prf: secret key not set (pvac_hip_ctx_set_secret)");
+    if (!c->have_digest) return fail(c, PVAC_EINVAL, "prf: H_digest unknown (gen_H, set_H or set_H_digest)");
+    if (!c->prf.aes_tables) {
+        hipError_t e = prf_upload_tables(c->stream);
+        if (e != hipSuccess) return hip_fail(c, e, "prf tables");
+        c->prf.aes_tables = true;
+    }
+    uint8_t m[64];
+    for (int i = 0; i < 4; ++i)
+        for (int b = 0; b < 8; ++b) m[8 * i + b] = (uint8_t)(c->prf.k[i] >> (8 * b));
+    for (int b = 0; b < 8; ++b) m[32 + b] = (uint8_t)(c->prm.canon_tag >> (8 * b));
+    std::memcpy(m + 40, c->H_digest, 24);
+    uint32_t w[16];
+    for (int i = 0; i < 16; ++i)
+        w[i] = (uint32_t)m[4 * i] << 24 | (uint32_t)m[4 * i + 1] << 16 | (uint32_t)m[4 * i + 2] << 8 | m[4 * i + 3];
+    sha_state st;
+    sha_init(st);
+    sha_compress(st, w);
+    std::memcpy(k.mid, st.h, 32);
+    uint64_t tail = 0;
+    for (int b = 0; b < 8; ++b) tail |= (uint64_t)c->H_digest[24 + b] << (8 * b);
+    k.hd_tail = tail;
+    static const char* const doms[6] = {"pvac.prf.r.1", "pvac.prf.r.2", "pvac.prf.r.3",
+                                        "pvac.prf.noise.1", "pvac.prf.noise.2", "pvac.prf.noise.3"};
+    for (int d = 0; d < 6; ++d) k.dom_hash[d] = fnv1a(doms[d]);
+    k.toep_hash = fnv1a("pvac.dom.toeplitz");
+    k.s_bits = c->prf.lpn_s.get();
+    k.s_words = c->prf.lpn_words;
+    k.tau_num = c->prf.tau_num;
+    k.tau_den = c->prf.tau_den;
+    return PVAC_OK;
+}
+
+int ensure_prf_scratch(pvac_hip_ctx* c, uint64_t cores) {
+    int rc = hip_fail(c, c->prf.req.grow_floor(cores * prf_request_bytes()), "alloc prf requests");
+    if (rc) return rc;
+    return hip_fail(c, c->prf.core.grow_floor(2 * cores), "alloc prf cores");
+}
+
+}  // namespace
+
+int pvac_hip_prf(pvac_hip_ctx* c, int kind, size_t n, const uint64_t* seeds, uint64_t* out) try {
+    if (!c || kind < 0 || kind > 7 || (n && (!seeds || !out))) return fail(c, PVAC_EINVAL, "prf: arguments");
+    if (!n) return PVAC_OK;
+    prf_consts k{};
+    int rc = prf_setup(c, k);
+    if (rc) return rc;
+    rc = ensure_prf_scratch(c, 3 * (uint64_t)n);
+    if (rc) return rc;
+    scoped_timer t(c, "prf");
+    return hip_fail(c, launch_prf(k, kind, seeds, n, c->prf.req.get(), c->prf.core.get(), out, c->stream), "prf");
+} catch (...) { return caught(c, "prf"); }
+
+// ---------------------------------------------------------------- enc_value
+namespace {
+// ops/encrypt.hpp:16-27 with the context's noise Params (the reference's defaults: noise_entropy_bits
+// 120, tuple2_fraction 0.55, depth_slope_bits 16; pvac_hip_ctx_set_noise); enc_value uses depth_hint 0
+void plan_noise(const pvac_hip_ctx* c, int depth, uint32_t& z2, uint32_t& z3) {
+    const uint32_t B = c->prm.B;
+    const double budget = c->prf.noise_bits + c->prf.noise_slope * std::max(0, depth);
+    const double per2 = 2.0 * std::log2((double)B), per3 = 3.0 * std::log2((double)B);
+    int a = std::max(0, (int)std::floor((budget * c->prf.noise_t2) / std::max(1e-6, per2)));
+    int b = std::max(0, (int)std::floor((budget * (1.0 - c->prf.noise_t2)) / std::max(1e-6, per3)));
+    if (a + b == 1) { if (b > 0) ++b; else ++a; }
+    z2 = (uint32_t)a;
+    z3 = (uint32_t)b;
+}
+}  // namespace
+
+int pvac_hip_enc_caps(pvac_hip_ctx* c, uint32_t* layers_per_value, uint32_t* edges_per_value, uint32_t* draws_hint) {
+    return pvac_hip_enc_caps_depth(c, 0, layers_per_value, edges_per_value, draws_hint);
+}
+
+int pvac_hip_enc_caps_depth(pvac_hip_ctx* c, int depth_hint, uint32_t* layers_per_value, uint32_t* edges_per_value,
+                            uint32_t* draws_hint) try {
+    if (!c) return PVAC_EINVAL;
+    uint32_t z2, z3;
+    plan_noise(c, depth_hint, z2, z3);
+    if ((uint64_t)8 + 2ull * z2 + 3ull * z3 > kEncPreMax)
+        return fail(c, PVAC_ENOSYS, "enc_caps: noise plan beyond 256 pre-merge edges per half (depth hint > 124 with the default Params)");
+    const uint32_t npre = 8 + 2 * z2 + 3 * z3;
+    if (layers_per_value) *layers_per_value = 2;
+    if (edges_per_value) *edges_per_value = 2 * npre;
+    // mask 2 + per half: nonce 2, signal 2*8 + 2*7, salts npre, noise picks/signs/coefficients, shuffle
+    if (draws_hint) *draws_hint = 2 + 2 * (2 + 16 + 14 + npre + z2 * 5 + z3 * 10 + npre) + 64;
+    return PVAC_OK;
+} catch (...) { return caught(c, "enc_caps"); }
+
+int pvac_hip_enc_value(pvac_hip_ctx* c, size_t n, const uint64_t* values, const uint64_t* rnd, uint32_t rnd_stride,
+                       pvac_ct_batch* C, uint32_t flags, uint32_t* status) {
+    return pvac_hip_enc_value_depth(c, n, values, rnd, rnd_stride, 0, C, flags, status);
+}
+
+int pvac_hip_enc_value_depth(pvac_hip_ctx* c, size_t n, const uint64_t* values, const uint64_t* rnd, uint32_t rnd_stride,
+                             int depth_hint, pvac_ct_batch* C, uint32_t flags, uint32_t* status) try {
+    if (!c || !C || (n && (!values || !rnd || !status))) return fail(c, PVAC_EINVAL, "enc_value: arguments");
+    if (!C->l_off || !C->l_cnt || !C->layers || !C->e_off || !C->e_cnt || !C->meta || !C->w_lo || !C->w_hi)
+        return fail(c, PVAC_EINVAL, "enc_value: output arrays");
+    const bool with_sigma = (flags & PVAC_ENC_WITH_SIGMA) != 0;
+    if (with_sigma && (!C->sigma || !c->H.ready || C->sigma_words != c->prm.m_bits / 64))
+        return fail(c, PVAC_EINVAL, "enc_value: WITH_SIGMA needs C->sigma (m_bits/64 words per edge) and H");
+    if (!c->powg.get()) return fail(c, PVAC_EINVAL, "enc_value: powg_B not set (pvac_hip_ctx_set_powg)");
+    C->n = n;
+    if (!n) return PVAC_OK;
+    prf_consts k{};
+    int rc = prf_setup(c, k);
+    if (rc) return rc;
+    enc_plan_args a{};
+    a.values = values;
+    a.rnd = rnd;
+    a.stride = rnd_stride;
+    a.B = c->prm.B;
+    plan_noise(c, depth_hint, a.Z2, a.Z3);
+    a.n = n;
+    a.canon = c->prm.canon_tag;
+    a.powg = c->powg.get();
+    const uint32_t npre = 8 + 2 * a.Z2 + 3 * a.Z3;
+    if ((uint64_t)8 + 2ull * a.Z2 + 3ull * a.Z3 > kEncPreMax)
+        return fail(c, PVAC_ENOSYS, "enc_value: noise plan beyond 256 pre-merge edges per half (depth hint > 124 with the default Params)");
+    const uint64_t cores = (uint64_t)n * enc_cores_per_value(a.Z2, a.Z3);
+    const uint64_t pe = (uint64_t)n * 2 * npre;
+    const uint32_t sw = c->prm.m_bits / 64;
+    // arena: halves | requests | cores | pre CSR (4 x n) | pre layers | meta, w_lo, w_hi, salt | sigma
+    auto al = [](uint64_t b) { return (b + 255) & ~255ull; };
+    const uint64_t off_req = al((uint64_t)2 * n * enc_half_bytes(npre));
+    const uint64_t off_core = off_req + al(cores * prf_request_bytes());
+    const uint64_t off_csr = off_core + al(cores * 16);
+    const uint64_t off_lay = off_csr + al((uint64_t)n * 32);
+    const uint64_t off_e = off_lay + al((uint64_t)n * 2 * sizeof(pvac_layer));
+    const uint64_t off_sig = off_e + al(pe * 32);
+    const uint64_t total = off_sig + (with_sigma ? al(pe * sw * 8) : 0);
+    if (const hipError_t ea = c->prf.enc_arena.grow(total, total)) return hip_fail(c, ea, "alloc enc scratch");
+    uint8_t* A = c->prf.enc_arena.get();
+    pvac_ct_batch pre{};
+    pre.n = n;
+    pre.l_off = (uint64_t*)(A + off_csr);
+    pre.l_cnt = pre.l_off + n;
+    pre.e_off = pre.l_cnt + n;
+    pre.e_cnt = pre.e_off + n;
+    pre.layers = (pvac_layer*)(A + off_lay);
+    pre.meta = (uint64_t*)(A + off_e);
+    pre.w_lo = pre.meta + pe;
+    pre.w_hi = pre.w_lo + pe;
+    uint64_t* pre_salt = pre.w_hi + pe;
+    pre.sigma = with_sigma ? (uint64_t*)(A + off_sig) : nullptr;
+    pre.sigma_words = with_sigma ? sw : 0;
+    scoped_timer t(c, "enc_value");
+    hipError_t e = launch_enc_plan(a, A, (prf_request*)(A + off_req), pre, pre_salt, status, c->stream);
+    if (e == hipSuccess) e = launch_prf_cores(k, A + off_req, cores, (uint64_t*)(A + off_core), c->stream);
+    if (e == hipSuccess) e = launch_enc_weights(a, A, (const uint64_t*)(A + off_core), pre, c->stream);
+    if (e == hipSuccess && with_sigma) e = launch_sigma(c->H, c->prm, pre, pre_salt, nullptr, c->num_cus, c->stream);
+    pvac_ct_batch out = *C;
+    if (!with_sigma) out.sigma = nullptr;
+    if (e == hipSuccess) e = launch_enc_finish(a, A, pre, out, status, c->stream);
+    return hip_fail(c, e, "enc_value");
+} catch (...) { return caught(c, "enc_value"); }
+
+int pvac_hip_base_R(pvac_hip_ctx* c, const pvac_ct_batch* X, uint64_t* R_out) try {
+    if (!c || !batch_ok(X) || (X->n && !R_out)) return fail(c, PVAC_EINVAL, "base_R: arguments");
+    if (!X->n) return PVAC_OK;
+    prf_consts k{};
+    int rc = prf_setup(c, k);
+    if (rc) return rc;
+    // layer slots are addressed through l_off / l_cnt on the device: gather every slot's seed
+    std::vector<uint64_t> lo(X->n), lc(X->n);
+    hipError_t e = hipMemcpyAsync(lo.data(), X->l_off, X->n * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(lc.data(), X->l_cnt, X->n * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return hip_fail(c, e, "base_R (offsets)");
+    uint64_t slots = 0;
+    for (uint64_t i = 0; i < X->n; ++i) slots = std::max(slots, lo[i] + lc[i]);
+    if (!slots) return PVAC_OK;
+    rc = ensure_prf_scratch(c, 4 * slots);   // 3 cores per slot + the BASE flags behind them
+    if (rc) return rc;
+    scoped_timer t(c, "base_R");
+    return hip_fail(c, launch_base_R(k, *X, slots, c->prf.req.get(), c->prf.core.get(), R_out, c->stream), "base_R");
+} catch (...) { return caught(c, "base_R"); }
+
+int pvac_hip_dec_value(pvac_hip_ctx* c, const pvac_ct_batch* X, const uint64_t* R_base, uint64_t* out,
+                       uint32_t* status) try {
+    if (!c || !batch_ok(X) || !out || !status || (X->n && !R_base)) return fail(c, PVAC_EINVAL, "dec_value: arguments");
+    if (!c->powg.get()) return fail(c, PVAC_EINVAL, "dec_value: powg_B not set (pvac_hip_ctx_set_powg)");
+    if (!X->n) return PVAC_OK;
+    int rc = ensure_scan(c, X->n);   // no plan scratch: a pending plan stays valid
+    if (rc) return rc;
+    rc = hip_fail(c, c->prf.dec_roff.grow_floor(X->n), "alloc dec offsets");
+    if (rc) return rc;
+    // dense per-cipher layer offsets (the batch may be capacity-padded)
+    hipError_t e = hipMemcpyAsync(c->prf.dec_roff.get(), X->l_cnt, X->n * 8, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = launch_exclusive_scan_u64(c->prf.dec_roff.get(), X->n, c->scan_scratch.get(), &c->ps.totals[0], c->stream);
+    unsigned long long total = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, &c->ps.totals[0], 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return hip_fail(c, e, "dec_value (offsets)");
+    const size_t need = dec_scratch_bytes(total);
+    e = c->prf.dec_scratch.grow(need, need);
+    if (e != hipSuccess) return hip_fail(c, e, "alloc dec scratch");
+    scoped_timer t(c, "dec_value");
+    return hip_fail(c,
+                    launch_dec_value(*X, R_base, c->powg.get(), c->prm.B, c->prf.dec_roff.get(), total, c->prf.dec_scratch.get(), out, status,
+                                     c->stream),
+                    "dec_value");
+} catch (...) { return caught(c, "dec_value"); }
+
+}  // extern "C"

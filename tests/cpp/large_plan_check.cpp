@@ -3,8 +3,8 @@
 // (cut_sub_batch). Host code only; built with ASan + UBSan by tests/test_large_plan.py.
 //
 // The expected values in the tables below were printed by the code as it stood BEFORE it moved into
-// large_plan.hpp (build_large_desc and rebase_desc in runtime.cpp, the sub-batch loop inside
-// run_large): the move must not change one of them. A change that is meant to change a layout or a
+// large_plan.hpp (build_large_desc and rebase_desc in the host runtime, the sub-batch loop inside
+// run_large, now in csrc/rt_mul.cpp): the move must not change one of them. A change that is meant to change a layout or a
 // launch size has to justify the new numbers and replace the rows.
 #include <cstdio>
 #include <cstdlib>

@@ -681,6 +681,14 @@ def test_ct_mul_api_errors_leave_context_usable(oracle):
     Cb2, plan2 = eng.ct_mul_plan(A, B)   # `plan` is stale from here on
     with pytest.raises(PvacError, match="latest"):
         eng.ct_mul(A, B, nonces=nonces, C_=Cb, plan=plan)
+    # the ct_add and compact plans share the pair scratch with ct_mul's: each makes a ct_mul plan stale
+    eng.ct_add(A, B)
+    with pytest.raises(PvacError, match="latest"):
+        eng.ct_mul(A, B, nonces=nonces, C_=Cb2, plan=plan2)
+    Cb3, plan3 = eng.ct_mul_plan(A, B)
+    eng.compact(_dev_batch(eng, xs, sigma=True))
+    with pytest.raises(PvacError, match="latest"):
+        eng.ct_mul(A, B, nonces=nonces, C_=Cb3, plan=plan3)
     big_a, big_b = _full_range_cipher(rng, 200, 64, dup_frac=0), _full_range_cipher(rng, 90, 64, dup_frac=0)
     with pytest.raises(PvacError, match="layers"):
         eng.ct_mul_plan(_dev_batch(eng, [big_a]), _dev_batch(eng, [big_b]))
@@ -692,6 +700,34 @@ def test_ct_mul_api_errors_leave_context_usable(oracle):
     for p, (x, y) in enumerate(zip(xs, ys)):
         base = int(loff[p]) + x.nL + y.nL
         ref = oracle.ct_mul(x, y, nz[2 * base:2 * base + 2 * x.nL * y.nL], canon_tag=0x55)
+        _assert_same(out[p], ref, layers_view=False)
+
+
+def test_ct_mul_plan_pending_across_dec_value(oracle):
+    """A pending ct_mul plan survives a dec_value of more ciphers than the pair scratch holds: 1,025
+    one-layer, one-edge ciphers, one above the scratch's floor of 1,024 pairs. dec_value needs the
+    scans' scratch only, so the plan's pair classes and records stay where they are: the exec is
+    bit-exact against the oracle and every pair keeps the reference order."""
+    from pvac_hfhe_cppbyv_amd import Engine
+    eng = Engine(device=0, canon_tag=0x56)
+    eng.set_powg(read_u64("powg_B.u64"))
+    rng = np.random.default_rng(0x56)
+    xs = [_full_range_cipher(rng, 2, 40, dup_frac=0) for _ in range(3)]
+    ys = [_full_range_cipher(rng, 2, 40, dup_frac=0) for _ in range(3)]
+    A, B = _dev_batch(eng, xs), _dev_batch(eng, ys)
+    Cb, plan = eng.ct_mul_plan(A, B)
+    nonces = eng.torch.empty(2 * plan.total_layer_slots, dtype=eng.torch.int64, device=eng.device)
+    eng.fill_random(nonces, 0x56)
+    many = _dev_batch(eng, [_full_range_cipher(rng, 1, 1, dup_frac=0) for _ in range(1025)])
+    vals, st = eng.dec_value(many, rng.integers(1, 2**63, 2 * 1025, dtype=np.uint64))
+    assert len(vals) == 1025 and len(st) == 1025
+    out = eng.ct_mul(A, B, nonces=nonces, C_=Cb, plan=plan).to_host()
+    assert list(eng.ct_mul_status(3)) == [0, 0, 0]
+    nz = nonces.cpu().numpy().view(np.uint64)
+    loff = Cb.l_off.cpu().numpy().view(np.uint64)
+    for p, (x, y) in enumerate(zip(xs, ys)):
+        base = int(loff[p]) + x.nL + y.nL
+        ref = oracle.ct_mul(x, y, nz[2 * base:2 * base + 2 * x.nL * y.nL], canon_tag=0x56)
         _assert_same(out[p], ref, layers_view=False)
 
 
