@@ -508,6 +508,51 @@ int pvac_hip_enc_caps_depth(pvac_hip_ctx* ctx, int depth_hint, uint32_t* layers_
                             uint32_t* draws_hint);
 int pvac_hip_enc_value_depth(pvac_hip_ctx* ctx, size_t n, const uint64_t* values, const uint64_t* rnd, uint32_t rnd_stride,
                              int depth_hint, pvac_ct_batch* C, uint32_t flags, uint32_t* status);
+/* A ragged batch of encryptions in one call: item i is a bare enc_fp_depth (one BASE layer, no mask,
+ * a plaintext of two words) or the masked enc_value_depth form, with its own depth hint, hence its
+ * own noise plan, and its own draw segment rnd[rnd_off .. rnd_off + rnd_cnt) of the DEVICE array rnd
+ * (rnd_words words). Draws are consumed in the reference's order: an FP item as one enc_fp_depth
+ * (nonce, signal picks, coefficients, salts, noise groups, shuffle); a VALUE item as mask, the -mask
+ * half, the v + mask half, exactly as pvac_hip_enc_value_depth. enc_text (utils/text.hpp:39-61) is a
+ * VALUE item (the length, hint 0) followed by one FP item per 15-byte block with hints 2, 3, ...
+ * Segments are per item because rejection sampling makes the number of draws data-dependent.
+ * items is HOST memory. pvac_hip_enc_items_caps gives the sizes: layer_slots = sum of halves (1 or 2),
+ * edge_slots = sum of halves x (8 + 2 Z2 + 3 Z3), draws_hint[i] (HOST, n words, nullable) a segment
+ * length that suffices unless rejections exceed its slack. pvac_hip_enc_items writes C as
+ * capacity-padded CSR: l_off = prefix sums of the halves, e_off = prefix sums of the pre-merge edge
+ * counts, e_cnt exact; C's index arrays hold n entries, C->layers layer_cap, the edge arrays (and
+ * C->sigma with PVAC_ENC_WITH_SIGMA) edge_cap slots. status (DEVICE, n u32) as for pvac_hip_enc_value:
+ * 0 ok, 1 the item's segment ran out (its rows are meaningless; its neighbours are unaffected), 2 a
+ * merged group cancelled exactly. Before anything is launched or written: PVAC_EINVAL for an unknown
+ * kind or a draw range outside rnd_words, PVAC_ENOSYS for a plan beyond 256 pre-merge edges per half
+ * (depth hint > 124 with the default Params), PVAC_ENOMEM when layer_cap / edge_cap are too small.
+ * Needs what pvac_hip_enc_value needs. Synchronises once (the item records' upload); the kernels are
+ * enqueued. pvac_hip_enc_value(_depth) keep their own kernels. */
+#define PVAC_ENC_ITEM_FP    0u  /* enc_fp_depth(pk, sk, Fp{v_lo, v_hi}, depth_hint), encrypt.hpp:162-258: 1 BASE layer */
+#define PVAC_ENC_ITEM_VALUE 1u  /* enc_value_depth(pk, sk, v_lo, depth_hint), :281-287: 2 layers (v_lo = 0: enc_zero_depth) */
+typedef struct pvac_enc_item {  /* HOST memory */
+    uint64_t v_lo, v_hi;        /* passed to the equations as given, no canonicalisation (the reference does none) */
+    int32_t  depth_hint;
+    uint32_t kind;
+    uint64_t rnd_off, rnd_cnt;  /* this item's draws: rnd[rnd_off .. rnd_off + rnd_cnt) */
+} pvac_enc_item;
+int pvac_hip_enc_items_caps(pvac_hip_ctx* ctx, size_t n, const pvac_enc_item* items, uint64_t* layer_slots,
+                            uint64_t* edge_slots, uint64_t* draws_hint);
+int pvac_hip_enc_items(pvac_hip_ctx* ctx, size_t n, const pvac_enc_item* items, const uint64_t* rnd, uint64_t rnd_words,
+                       pvac_ct_batch* C, uint64_t layer_cap, uint64_t edge_cap, uint32_t flags, uint32_t* status);
+
+/* Text packing (utils/text.hpp:15-37, 63-87), HOST memory, no context. pvac_text_pack: block b of msg
+ * (up to 15 bytes, little-endian) as fp_from_words(lo, hi) into v_out[2 b], v_out[2 b + 1];
+ * *blocks = ceil(len / 15); PVAC_ENOMEM (with *blocks set) when block_cap is smaller. pvac_text_unpack:
+ * dec holds 2 words per cipher of one message, cipher 0 the length; out receives
+ * min(length, 15 (n_ciphers - 1)) bytes and *len that count; *flags bit 0: the length's high word was
+ * not 0 (the reference warns and goes on), bit 1: the length was clipped to the blocks present.
+ * n_ciphers = 0 is the empty message. PVAC_ENOMEM (with *len set) when cap is smaller. */
+#define PVAC_TEXT_LEN_HI 0x1u
+#define PVAC_TEXT_LEN_CLIPPED 0x2u
+int pvac_text_pack(const uint8_t* msg, size_t len, uint64_t* v_out, size_t block_cap, size_t* blocks);
+int pvac_text_unpack(const uint64_t* dec, size_t n_ciphers, uint8_t* out, size_t cap, size_t* len, uint32_t* flags);
+
 /* prf_R of every BASE layer of X (ops/decrypt.hpp:44-46): R_out device, 2 words per layer SLOT
  * (slots addressed by l_off/l_cnt; PROD slots get 0) — the R_base input of pvac_hip_dec_value. */
 int pvac_hip_base_R(pvac_hip_ctx* ctx, const pvac_ct_batch* X, uint64_t* R_out);

@@ -801,6 +801,142 @@ public:
         return out;
     }
 
+    // A ragged batch of encryptions (pvac_hip_enc_items): item i is enc_fp_depth(Fp{v_lo, v_hi}, hint)
+    // (kind PVAC_ENC_ITEM_FP) or enc_value_depth(v_lo, hint) (PVAC_ENC_ITEM_VALUE). Item i takes
+    // draws_hint[i] (pvac_hip_enc_items_caps) consecutive words of rnd, in item order: the per-value
+    // stride rule of enc_value. An item whose rejection sampling outruns its words (status 1) is
+    // re-run with its own draws extended, prefix kept. A plan beyond 256 pre-merge edges
+    // (depth hint > 124 with the default noise Params) throws Error(PVAC_ENOSYS) before any draw.
+    struct EncItem {
+        uint32_t kind;
+        uint64_t v_lo, v_hi;
+        int depth_hint;
+    };
+    // words of rnd each item of enc_items takes (for a caller that replays a recorded stream)
+    template <class PubKeyT>
+    std::vector<uint64_t> enc_items_draws(const PubKeyT& pk, const std::vector<EncItem>& its) {
+        check(pvac_hip_ctx_set_noise(ctx_, (double)pk.prm.noise_entropy_bits, (double)pk.prm.tuple2_fraction,
+                                     (double)pk.prm.depth_slope_bits));
+        std::vector<pvac_enc_item> items(its.size());
+        for (size_t i = 0; i < its.size(); ++i)
+            items[i] = pvac_enc_item{its[i].v_lo, its[i].v_hi, its[i].depth_hint, its[i].kind, 0, 0};
+        std::vector<uint64_t> hint(its.size());
+        check(pvac_hip_enc_items_caps(ctx_, items.size(), items.data(), nullptr, nullptr, hint.data()));
+        return hint;
+    }
+
+    template <class PubKeyT, class SecKeyT, class CipherT>
+    std::vector<CipherT> enc_items(const PubKeyT& pk, const SecKeyT& sk, const std::vector<EncItem>& its, bool with_sigma,
+                                   const RandomSource& rnd) {
+        const size_t n = its.size();
+        if (!n) return {};
+        ensure_keys(pk, sk);
+        if (with_sigma) ensure_H(pk);
+        std::vector<pvac_enc_item> items(n);
+        for (size_t i = 0; i < n; ++i) items[i] = pvac_enc_item{its[i].v_lo, its[i].v_hi, its[i].depth_hint, its[i].kind, 0, 0};
+        std::vector<uint64_t> hint(n);
+        uint64_t ls = 0, es = 0;
+        check(pvac_hip_enc_items_caps(ctx_, n, items.data(), &ls, &es, hint.data()));
+        std::vector<std::vector<uint64_t>> draws(n);
+        for (size_t i = 0; i < n; ++i) {
+            draws[i].resize((size_t)hint[i]);
+            for (auto& x : draws[i]) x = rnd();
+        }
+        std::vector<CipherT> out(n);
+        std::vector<size_t> todo(n);
+        for (size_t i = 0; i < n; ++i) todo[i] = i;
+        for (int round = 0; !todo.empty(); ++round) {
+            if (round > 12) throw Error(PVAC_EINVAL, "enc_items: random source keeps being rejected");
+            const size_t m = todo.size();
+            std::vector<pvac_enc_item> sub(m);
+            std::vector<uint64_t> flat;
+            for (size_t k = 0; k < m; ++k) {
+                sub[k] = items[todo[k]];
+                sub[k].rnd_off = flat.size();
+                sub[k].rnd_cnt = draws[todo[k]].size();
+                flat.insert(flat.end(), draws[todo[k]].begin(), draws[todo[k]].end());
+            }
+            check(pvac_hip_enc_items_caps(ctx_, m, sub.data(), &ls, &es, nullptr));
+            detail::dev_array<uint64_t> d_r(flat.size());
+            d_r.upload(flat.data(), flat.size(), stream_);
+            detail::batch c;
+            c.d_l_off.alloc(m); c.d_l_cnt.alloc(m); c.d_e_off.alloc(m); c.d_e_cnt.alloc(m);
+            detail::alloc_out(c, m, ls, es, sigma_words(), with_sigma);
+            pvac_ct_batch vc = c.view(with_sigma);
+            vc.n = m;
+            detail::dev_array<uint32_t> st(m);
+            check(pvac_hip_enc_items(ctx_, m, sub.data(), d_r.p, flat.size(), &vc, ls, es, with_sigma ? PVAC_ENC_WITH_SIGMA : 0,
+                                     st.p));
+            std::vector<uint32_t> status(m);
+            st.download(status.data(), m, stream_);
+            std::vector<CipherT> got = detail::from_device<CipherT>(c, m, ls, es, prm_.m_bits, with_sigma, stream_);
+            std::vector<size_t> redo;
+            for (size_t k = 0; k < m; ++k) {
+                if (status[k] == 2) throw Error(PVAC_EINVAL, "enc_items: a merged edge group cancelled (p ~ 1/p)");
+                if (status[k] == 1) {
+                    std::vector<uint64_t>& d = draws[todo[k]];
+                    const size_t more = d.size();
+                    for (size_t j = 0; j < more; ++j) d.push_back(rnd());
+                    redo.push_back(todo[k]);
+                } else {
+                    out[todo[k]] = std::move(got[k]);
+                }
+            }
+            todo.swap(redo);
+        }
+        return out;
+    }
+
+    // enc_text (utils/text.hpp:39-61) of every message in one enc_items call: per message the length
+    // as a value item (hint 0), then its 15-byte blocks as bare items with hints 2, 3, ... With the
+    // default noise Params a message of more than 123 blocks (1,845 bytes) needs hint 125 and throws
+    // Error(PVAC_ENOSYS).
+    template <class PubKeyT, class SecKeyT, class CipherT>
+    std::vector<std::vector<CipherT>> enc_text(const PubKeyT& pk, const SecKeyT& sk, const std::vector<std::string>& msgs,
+                                               bool with_sigma, const RandomSource& rnd) {
+        std::vector<EncItem> its;
+        std::vector<size_t> first{0};
+        for (const std::string& m : msgs) {
+            size_t nb = 0;
+            std::vector<uint64_t> v(2 * (m.size() / 15 + 1));
+            const int rc = pvac_text_pack((const uint8_t*)m.data(), m.size(), v.data(), v.size() / 2, &nb);
+            if (rc) throw Error(rc, "pvac_text_pack");
+            its.push_back(EncItem{PVAC_ENC_ITEM_VALUE, (uint64_t)m.size(), 0, 0});
+            for (size_t b = 0; b < nb; ++b) its.push_back(EncItem{PVAC_ENC_ITEM_FP, v[2 * b], v[2 * b + 1], (int)(2 + b)});
+            first.push_back(its.size());
+        }
+        std::vector<CipherT> all = enc_items<PubKeyT, SecKeyT, CipherT>(pk, sk, its, with_sigma, rnd);
+        std::vector<std::vector<CipherT>> out(msgs.size());
+        for (size_t m = 0; m < msgs.size(); ++m)
+            out[m].assign(std::make_move_iterator(all.begin() + first[m]), std::make_move_iterator(all.begin() + first[m + 1]));
+        return out;
+    }
+
+    // dec_text (utils/text.hpp:63-87) of every message: one batched dec_value, then pvac_text_unpack
+    // (a length whose high word is not 0 is used as the reference uses it: the low word counts)
+    template <class PubKeyT, class SecKeyT, class CipherT, class FpT>
+    std::vector<std::string> dec_text(const PubKeyT& pk, const SecKeyT& sk, const std::vector<const std::vector<CipherT>*>& msgs) {
+        std::vector<const CipherT*> p;
+        for (const auto* m : msgs)
+            for (const CipherT& c : *m) p.push_back(&c);
+        const std::vector<FpT> vals = dec_value<PubKeyT, SecKeyT, CipherT, FpT>(pk, sk, p);
+        std::vector<std::string> out;
+        size_t at = 0;
+        for (const auto* m : msgs) {
+            std::vector<uint64_t> d(2 * m->size() + 2);
+            for (size_t k = 0; k < m->size(); ++k) { d[2 * k] = vals[at + k].lo; d[2 * k + 1] = vals[at + k].hi; }
+            at += m->size();
+            std::string s(15 * m->size(), '\0');
+            size_t len = 0;
+            uint32_t flags = 0;
+            const int rc = pvac_text_unpack(d.data(), m->size(), (uint8_t*)&s[0], s.size(), &len, &flags);
+            if (rc) throw Error(rc, "pvac_text_unpack");
+            s.resize(len);
+            out.push_back(std::move(s));
+        }
+        return out;
+    }
+
     // Batched dec_value (ops/decrypt.hpp:12-89): prf_R of every BASE layer on the device
     // (pvac_hip_base_R), then the R-tree, inverses and weighted sum (pvac_hip_dec_value).
     template <class PubKeyT, class SecKeyT, class CipherT, class FpT>
@@ -1352,6 +1488,44 @@ auto dec_value_batch(const PubKeyT& pk, const SecKeyT& sk, const std::vector<Cip
     std::vector<const CipherT*> p;
     for (auto& x : cs) p.push_back(&x);
     return engine_for(pk).template dec_value<PubKeyT, SecKeyT, CipherT, FpT>(pk, sk, p);
+}
+
+// ---- bare enc_fp_depth and text (ops/encrypt.hpp:162-258, utils/text.hpp:39-87) ------------
+// enc_fp_depth: one BASE layer, no mask; v's two words go to the equations as given.
+template <class CipherT, class PubKeyT, class SecKeyT, class FpT>
+CipherT enc_fp_depth(const PubKeyT& pk, const SecKeyT& sk, const FpT& v, int depth_hint,
+                     const RandomSource& rnd = os_random_u64) {
+    return engine_for(pk).template enc_items<PubKeyT, SecKeyT, CipherT>(
+        pk, sk, {Engine::EncItem{PVAC_ENC_ITEM_FP, v.lo, v.hi, depth_hint}}, true, rnd)[0];
+}
+
+// enc_text: the length, then one cipher per 15-byte block with depth hints 2, 3, ...; more than 123
+// blocks (1,845 bytes) under the default noise Params throw Error(PVAC_ENOSYS).
+template <class CipherT, class PubKeyT, class SecKeyT>
+std::vector<std::vector<CipherT>> enc_text_batch(const PubKeyT& pk, const SecKeyT& sk, const std::vector<std::string>& msgs,
+                                                 bool with_sigma = true, const RandomSource& rnd = os_random_u64) {
+    return engine_for(pk).template enc_text<PubKeyT, SecKeyT, CipherT>(pk, sk, msgs, with_sigma, rnd);
+}
+
+template <class CipherT, class PubKeyT, class SecKeyT>
+std::vector<CipherT> enc_text(const PubKeyT& pk, const SecKeyT& sk, const std::string& msg,
+                              const RandomSource& rnd = os_random_u64) {
+    return std::move(enc_text_batch<CipherT>(pk, sk, std::vector<std::string>{msg}, true, rnd)[0]);
+}
+
+template <class PubKeyT, class SecKeyT, class CipherT>
+std::vector<std::string> dec_text_batch(const PubKeyT& pk, const SecKeyT& sk, const std::vector<std::vector<CipherT>>& msgs) {
+    using FpT = std::decay_t<decltype(std::declval<CipherT&>().E[0].w)>;
+    std::vector<const std::vector<CipherT>*> p;
+    for (const auto& m : msgs) p.push_back(&m);
+    return engine_for(pk).template dec_text<PubKeyT, SecKeyT, CipherT, FpT>(pk, sk, p);
+}
+
+template <class PubKeyT, class SecKeyT, class CipherT>
+std::string dec_text(const PubKeyT& pk, const SecKeyT& sk, const std::vector<CipherT>& cts) {
+    using FpT = std::decay_t<decltype(std::declval<CipherT&>().E[0].w)>;
+    return engine_for(pk).template dec_text<PubKeyT, SecKeyT, CipherT, FpT>(
+        pk, sk, std::vector<const std::vector<CipherT>*>{&cts})[0];
 }
 
 // ---- .ct files (the reference's tests/add.cpp:22-155 format) through the native codec ------

@@ -31,6 +31,8 @@ CHAIN_STAGE_INPUTS = 0x200
 CHAIN_IMG_BATCH2 = 0x400
 CHAIN_MAX_DEPTH = 32
 ENC_WITH_SIGMA = 0x1
+ENC_ITEM_FP, ENC_ITEM_VALUE = 0, 1
+TEXT_LEN_HI, TEXT_LEN_CLIPPED = 0x1, 0x2
 
 P = (1 << 127) - 1
 
@@ -68,6 +70,11 @@ class CtBatch(C.Structure):
     _fields_ = [("n", C.c_uint64), ("l_off", C.c_void_p), ("l_cnt", C.c_void_p), ("layers", C.c_void_p),
                 ("e_off", C.c_void_p), ("e_cnt", C.c_void_p), ("meta", C.c_void_p), ("w_lo", C.c_void_p),
                 ("w_hi", C.c_void_p), ("sigma", C.c_void_p), ("sigma_words", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class EncItem(C.Structure):
+    _fields_ = [("v_lo", C.c_uint64), ("v_hi", C.c_uint64), ("depth_hint", C.c_int32), ("kind", C.c_uint32),
+                ("rnd_off", C.c_uint64), ("rnd_cnt", C.c_uint64)]
 
 
 class Plan(C.Structure):
@@ -173,6 +180,10 @@ def load_library(path: str = _LIB_PATH) -> C.CDLL:
         "pvac_hip_enc_value": ([vp, C.c_size_t, vp, vp, u32, C.POINTER(CtBatch), u32, vp], i32),
         "pvac_hip_enc_caps_depth": ([vp, i32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)], i32),
         "pvac_hip_enc_value_depth": ([vp, C.c_size_t, vp, vp, u32, i32, C.POINTER(CtBatch), u32, vp], i32),
+        "pvac_hip_enc_items_caps": ([vp, C.c_size_t, vp, C.POINTER(u64), C.POINTER(u64), vp], i32),
+        "pvac_hip_enc_items": ([vp, C.c_size_t, vp, vp, u64, C.POINTER(CtBatch), u64, u64, u32, vp], i32),
+        "pvac_text_pack": ([vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)], i32),
+        "pvac_text_unpack": ([vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(u32)], i32),
         "pvac_hip_base_R": ([vp, C.POINTER(CtBatch), vp], i32),
         "pvac_hip_dec_value": ([vp, C.POINTER(CtBatch), vp, vp, vp], i32),
         "pvac_ct_scan": ([vp, C.c_size_t, vp], i32),
@@ -185,6 +196,33 @@ def load_library(path: str = _LIB_PATH) -> C.CDLL:
         f.argtypes = args
         f.restype = res
     return lib
+
+
+# ------------------------------------------------------------------------------ text packing (host)
+def text_pack(msg: bytes, lib: C.CDLL | None = None):
+    """pvac_text_pack: the 15-byte blocks of msg as (blocks, 2) u64 Fp words (utils/text.hpp:15-26)."""
+    lib = lib or load_library()
+    msg = bytes(msg)
+    nb = C.c_size_t()
+    out = np.zeros((-(-len(msg) // 15), 2), np.uint64)
+    rc = lib.pvac_text_pack(C.c_char_p(msg), len(msg), C.c_void_p(out.ctypes.data), len(out), C.byref(nb))
+    if rc != 0 or nb.value != len(out):
+        raise PvacError(f"pvac_text_pack: {rc}")
+    return out
+
+
+def text_unpack(dec, lib: C.CDLL | None = None):
+    """pvac_text_unpack: dec = (n_ciphers, 2) u64 decrypted words of one message, cipher 0 the length.
+    Returns (bytes, flags)."""
+    lib = lib or load_library()
+    d = np.ascontiguousarray(np.asarray(dec, dtype=np.uint64).reshape(-1, 2))
+    cap = 15 * max(len(d) - 1, 0)
+    out = C.create_string_buffer(max(cap, 1))
+    n, fl = C.c_size_t(), C.c_uint32()
+    rc = lib.pvac_text_unpack(C.c_void_p(d.ctypes.data), len(d), out, cap, C.byref(n), C.byref(fl))
+    if rc != 0:
+        raise PvacError(f"pvac_text_unpack: {rc}")
+    return out.raw[:n.value], fl.value
 
 
 # ------------------------------------------------------------------------------ host ciphers
@@ -373,6 +411,90 @@ class Engine:
                                                       C.c_void_p(rnd.data_ptr()), stride, int(depth), C.byref(sc),
                                                       ENC_WITH_SIGMA if sigma else 0, C.c_void_p(status.data_ptr())))
         return C_, status.cpu().numpy().view(np.uint32)[:n]
+
+    # ---- ragged encryption: per-item kind, plaintext, depth hint and draw segment
+    @staticmethod
+    def _items(items):
+        """items: EncItem array, or an iterable of (kind, v, depth_hint, rnd_off, rnd_cnt) with v an int
+        below 2^128 (its two words are passed as given)."""
+        if isinstance(items, C.Array):
+            return items
+        items = list(items)
+        arr = (EncItem * max(len(items), 1))()
+        for i, (kind, v, hint, off, cnt) in enumerate(items):
+            arr[i] = EncItem(int(v) & (2**64 - 1), int(v) >> 64, int(hint), int(kind), int(off), int(cnt))
+        arr._n = len(items)
+        return arr
+
+    def enc_items_caps(self, items):
+        """(layer_slots, edge_slots, draws_hint numpy u64 per item) of a batch of items."""
+        arr = self._items(items)
+        n = getattr(arr, "_n", len(arr))
+        ls, es = C.c_uint64(), C.c_uint64()
+        dh = np.zeros(max(n, 1), np.uint64)
+        self._check(self.lib.pvac_hip_enc_items_caps(self.ctx, n, C.cast(arr, C.c_void_p), C.byref(ls), C.byref(es),
+                                                     C.c_void_p(dh.ctypes.data)))
+        return ls.value, es.value, dh[:n]
+
+    def enc_items(self, items, rnd, sigma=False, caps=None):
+        """One launch sequence over a ragged batch: item i = (kind, v, depth_hint, rnd_off, rnd_cnt) is
+        enc_fp_depth(v, hint) (ENC_ITEM_FP, one layer) or enc_value_depth(v, hint) (ENC_ITEM_VALUE) from the
+        draws rnd[rnd_off : rnd_off + rnd_cnt] (rnd: flat u64 host array or device tensor). caps =
+        (layer_slots, edge_slots) overrides the output sizes. Returns (DeviceBatch, status numpy u32)."""
+        torch = self.torch
+        arr = self._items(items)
+        n = getattr(arr, "_n", len(arr))
+        if isinstance(rnd, np.ndarray):
+            rnd = _t(np.ascontiguousarray(rnd.reshape(-1), np.uint64) if rnd.size else np.zeros(1, np.uint64)).to(self.device)
+            words = rnd.numel() if n else 0
+        else:
+            words = rnd.numel()
+        ls, es = caps if caps is not None else self.enc_items_caps(arr)[:2]
+        C_ = DeviceBatch.empty(n, ls, es, self.device, sigma=sigma)
+        status = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        sc = C_.struct()
+        self._check(self.lib.pvac_hip_enc_items(self.ctx, n, C.cast(arr, C.c_void_p), C.c_void_p(rnd.data_ptr()), words,
+                                                C.byref(sc), int(ls), int(es), ENC_WITH_SIGMA if sigma else 0,
+                                                C.c_void_p(status.data_ptr())))
+        return C_, status.cpu().numpy().view(np.uint32)[:n]
+
+    def text_items(self, msgs):
+        """enc_text's items (utils/text.hpp:39-61) without draw segments: per message a VALUE item (the
+        length, hint 0), then an FP item per 15-byte block with hints 2, 3, ... Returns (list of [kind, v,
+        hint], msg_off) with msg_off[m] the first cipher of message m (len(msgs) + 1 entries)."""
+        items, off = [], [0]
+        for m in msgs:
+            m = bytes(m)
+            items.append([ENC_ITEM_VALUE, len(m), 0])
+            for b, (lo, hi) in enumerate(text_pack(m, self.lib)):
+                items.append([ENC_ITEM_FP, int(lo) | (int(hi) << 64), 2 + b])
+            off.append(len(items))
+        return items, off
+
+    def enc_text(self, msgs, rnd, rnd_off=None, sigma=True):
+        """enc_text of every message in one call. rnd: flat u64 draws; rnd_off: per cipher (in message
+        order: length, then blocks) its (offset, count) into rnd, or None for consecutive segments of
+        enc_items_caps' draws_hint. Returns (DeviceBatch, msg_off, status): message m is ciphers
+        msg_off[m] .. msg_off[m + 1], in the reference's order (write them with codec.write_ct)."""
+        items, moff = self.text_items(msgs)
+        if rnd_off is None:
+            hint = self.enc_items_caps([(k, v, h, 0, 0) for k, v, h in items])[2]
+            starts = np.concatenate([[0], np.cumsum(hint)[:-1]]) if len(items) else []
+            rnd_off = [(int(s), int(c)) for s, c in zip(starts, hint)]
+        full = [(k, v, h, o, c) for (k, v, h), (o, c) in zip(items, rnd_off)]
+        C_, status = self.enc_items(full, rnd, sigma=sigma)
+        return C_, moff, status
+
+    def dec_text(self, X: DeviceBatch, msg_off):
+        """dec_text (utils/text.hpp:63-87) of every message of X: base_R, dec_value, pvac_text_unpack."""
+        vals, st = self.dec_value(X, self.base_R(X))
+        if st.any():
+            raise PvacError(f"dec_text: dec_value status {st[st != 0][:4]}")
+        out = []
+        for m in range(len(msg_off) - 1):
+            d = [[v & (2**64 - 1), v >> 64] for v in vals[msg_off[m]:msg_off[m + 1]]]
+            out.append(text_unpack(np.array(d, np.uint64).reshape(-1, 2), self.lib)[0])
+        return out
 
     def base_R(self, X: DeviceBatch):
         """prf_R of every BASE layer slot of X (device tensor, 2 int64 words per slot)."""

@@ -222,7 +222,57 @@ hipError_t launch_enc_weights(const enc_plan_args& a, void* halves, const uint64
 hipError_t launch_enc_finish(const enc_plan_args& a, const void* halves, const pvac_ct_batch& pre, pvac_ct_batch& C,
                              uint32_t* status, hipStream_t st);
 
-// ---- dec_value (k_dec.hip): BASE-layer R supplied, PROD R tree, inversions, signed edge sum
+// ---- enc_items (k_enc_items.hip): a ragged batch of enc_fp_depth / enc_value_depth items, each with
+// its own noise plan, plaintext and draw segment. Halves (one enc_fp_depth each) are numbered through
+// the batch: item i owns halves [half_off, half_off + halves) = its output layers, and half h owns
+// pre-merge edge slots [pre_off + h npre, pre_off + (h + 1) npre): the ragged structure-of-arrays
+// scratch (key, salt, r, grp, slot) and the pre-merge batch are both addressed by those slots.
+struct enc_item_rec {         // one per item, built and uploaded by the host
+    uint64_t v_lo, v_hi;      // plaintext as given (VALUE items: v_lo)
+    uint64_t rnd_off;         // the item's draws: rnd[rnd_off .. rnd_off + rnd_cnt)
+    uint32_t rnd_cnt;
+    uint32_t Z2, Z3;          // its noise plan; npre = 8 + 2 Z2 + 3 Z3 <= kEncPreMax
+    uint32_t halves;          // 1 = bare enc_fp_depth, 2 = the masked value form
+    uint64_t half_off;        // = C.l_off[i]
+    uint64_t pre_off;         // = C.e_off[i]
+    uint64_t req_off;         // first PRF request; a half takes 3 max(Z2 + Z3, 1)
+};
+static_assert(sizeof(enc_item_rec) == 64, "enc_item_rec is one cache line");
+struct enc_half_hdr {         // one per half, written by k_enc_items_plan
+    uint64_t nlo, nhi, ztag;
+    uint64_t vlo, vhi;        // the value this half encrypts
+    uint64_t pre_off;         // its first pre-edge slot
+    uint64_t req_off;         // its first PRF request = its first core
+    uint32_t npre, nout;
+    uint32_t Z2, Z3;
+};
+struct enc_items_args {
+    uint64_t n;                    // items
+    uint64_t n_work;               // entries of `work`
+    uint64_t n_halves;
+    const enc_item_rec* recs;
+    const uint32_t* perm;          // item order of the plan kernel: pre-merge edges (halves x npre) descending
+    const uint64_t* work;          // half << 16 | group; group 0 = the signal equation, g + 1 = noise group g
+    const uint64_t* rnd;
+    const uint64_t* powg;          // B x (lo, hi)
+    uint64_t canon;
+    uint32_t B, pad;
+    enc_half_hdr* hdr;             // [halves]
+    uint32_t* key;                 // [pre-edge slots] idx | ch << 16, creation order
+    uint64_t* salt;                // ... the make_edge salts (the sigma launch's salts)
+    uint64_t *rlo, *rhi;           // ... drawn coefficients (0 where the equations solve them)
+    uint8_t *grp, *slot;           // ... compact_edges group of each pre-edge; output slot -> group
+};
+// 1. per item: draws, merge groups, shuffle, PRF requests, the pre-merge batch `pre` and status
+hipError_t launch_enc_items_plan(const enc_items_args& a, prf_request* req, pvac_ct_batch& pre, uint32_t* status,
+                                 hipStream_t st);
+// 2. per (half, group): R, the group's delta, its solved coefficient, its edges' weights -> pre.w_lo / w_hi
+hipError_t launch_enc_items_weights(const enc_items_args& a, const uint64_t* cores, pvac_ct_batch& pre, hipStream_t st);
+// 3. per item: merged groups (fp_add chains, sigma XOR) in shuffled order -> C
+hipError_t launch_enc_items_finish(const enc_items_args& a, const pvac_ct_batch& pre, pvac_ct_batch& C, uint32_t* status,
+                                   hipStream_t st);
+
+// ---- dec_value (k_dec.hip):BASE-layer R supplied, PROD R tree, inversions, signed edge sum
 size_t dec_scratch_bytes(uint64_t total_layers);
 hipError_t launch_dec_value(const pvac_ct_batch& X, const uint64_t* Rbase, const uint64_t* powg, uint32_t Bm,
                             const uint64_t* roff, uint64_t total_layers, void* scratch, uint64_t* out,

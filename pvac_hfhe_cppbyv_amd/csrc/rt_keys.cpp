@@ -248,6 +248,172 @@ int pvac_hip_enc_value_depth(pvac_hip_ctx* c, size_t n, const uint64_t* values, 
     return hip_fail(c, e, "enc_value");
 } catch (...) { return caught(c, "enc_value"); }
 
+// ---------------------------------------------------------------- enc_items
+namespace {
+struct item_plan {
+    uint32_t z2, z3, npre, halves;
+};
+// kinds and plans of a batch of items; PVAC_EINVAL / PVAC_ENOSYS before anything else happens
+int plan_items(pvac_hip_ctx* c, size_t n, const pvac_enc_item* items, std::vector<item_plan>& plans, const char* who) {
+    plans.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (items[i].kind != PVAC_ENC_ITEM_FP && items[i].kind != PVAC_ENC_ITEM_VALUE)
+            return fail(c, PVAC_EINVAL, std::string(who) + ": unknown item kind");
+        item_plan& p = plans[i];
+        plan_noise(c, items[i].depth_hint, p.z2, p.z3);
+        if ((uint64_t)8 + 2ull * p.z2 + 3ull * p.z3 > kEncPreMax)
+            return fail(c, PVAC_ENOSYS, std::string(who) + ": noise plan beyond 256 pre-merge edges per half (depth hint > 124 with the default Params)");
+        p.npre = 8 + 2 * p.z2 + 3 * p.z3;
+        p.halves = items[i].kind == PVAC_ENC_ITEM_VALUE ? 2 : 1;
+    }
+    return PVAC_OK;
+}
+}  // namespace
+
+int pvac_hip_enc_items_caps(pvac_hip_ctx* c, size_t n, const pvac_enc_item* items, uint64_t* layer_slots,
+                            uint64_t* edge_slots, uint64_t* draws_hint) try {
+    if (!c || (n && !items)) return fail(c, PVAC_EINVAL, "enc_items_caps: arguments");
+    std::vector<item_plan> plans;
+    const int rc = plan_items(c, n, items, plans, "enc_items_caps");
+    if (rc) return rc;
+    uint64_t ls = 0, es = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const item_plan& p = plans[i];
+        ls += p.halves;
+        es += (uint64_t)p.halves * p.npre;
+        // per half: nonce 2, signal 2*8 + 2*7, salts npre, noise picks/signs/coefficients, shuffle; a value's mask 2
+        const uint64_t half = 2 + 16 + 14 + p.npre + p.z2 * 5ull + p.z3 * 10ull + p.npre;
+        if (draws_hint) draws_hint[i] = p.halves == 2 ? 2 + 2 * half + 64 : half + 32;
+    }
+    if (layer_slots) *layer_slots = ls;
+    if (edge_slots) *edge_slots = es;
+    return PVAC_OK;
+} catch (...) { return caught(c, "enc_items_caps"); }
+
+int pvac_hip_enc_items(pvac_hip_ctx* c, size_t n, const pvac_enc_item* items, const uint64_t* rnd, uint64_t rnd_words,
+                       pvac_ct_batch* C, uint64_t layer_cap, uint64_t edge_cap, uint32_t flags, uint32_t* status) try {
+    if (!c || !C || (n && (!items || !rnd || !status))) return fail(c, PVAC_EINVAL, "enc_items: arguments");
+    if (!C->l_off || !C->l_cnt || !C->layers || !C->e_off || !C->e_cnt || !C->meta || !C->w_lo || !C->w_hi)
+        return fail(c, PVAC_EINVAL, "enc_items: output arrays");
+    const bool with_sigma = (flags & PVAC_ENC_WITH_SIGMA) != 0;
+    if (with_sigma && (!C->sigma || !c->H.ready || C->sigma_words != c->prm.m_bits / 64))
+        return fail(c, PVAC_EINVAL, "enc_items: WITH_SIGMA needs C->sigma (m_bits/64 words per edge) and H");
+    if (!c->powg.get()) return fail(c, PVAC_EINVAL, "enc_items: powg_B not set (pvac_hip_ctx_set_powg)");
+    if (n > 0x7FFFFFFFull) return fail(c, PVAC_EINVAL, "enc_items: more than 2^31 - 1 items");
+    std::vector<item_plan> plans;
+    int rc = plan_items(c, n, items, plans, "enc_items");
+    if (rc) return rc;
+    for (size_t i = 0; i < n; ++i)
+        if (items[i].rnd_off > rnd_words || items[i].rnd_cnt > rnd_words - items[i].rnd_off)
+            return fail(c, PVAC_EINVAL, "enc_items: an item's draw range lies outside rnd_words");
+    // one host image: records | work list | permutation (uploaded in one copy)
+    std::vector<enc_item_rec> recs(n);
+    std::vector<uint64_t> work;
+    uint64_t halves = 0, pe = 0, cores = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const item_plan& p = plans[i];
+        enc_item_rec& r = recs[i];
+        r.v_lo = items[i].v_lo;
+        r.v_hi = items[i].v_hi;
+        r.rnd_off = items[i].rnd_off;
+        r.rnd_cnt = (uint32_t)std::min<uint64_t>(items[i].rnd_cnt, 0xFFFFFFFFull);
+        r.Z2 = p.z2;
+        r.Z3 = p.z3;
+        r.halves = p.halves;
+        r.half_off = halves;
+        r.pre_off = pe;
+        r.req_off = cores;
+        for (uint32_t h = 0; h < p.halves; ++h)
+            for (uint32_t g = 0; g <= p.z2 + p.z3; ++g) work.push_back((halves + h) << 16 | g);
+        halves += p.halves;
+        pe += (uint64_t)p.halves * p.npre;
+        cores += (uint64_t)p.halves * 3 * std::max(p.z2 + p.z3, 1u);
+    }
+    if (halves > layer_cap || pe > edge_cap)
+        return fail(c, PVAC_ENOMEM, "enc_items: layer_cap / edge_cap below pvac_hip_enc_items_caps");
+    C->n = n;
+    if (!n) return PVAC_OK;
+    std::vector<uint32_t> perm(n);
+    for (size_t i = 0; i < n; ++i) perm[i] = (uint32_t)i;
+    std::stable_sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) {
+        return (uint64_t)plans[x].npre * plans[x].halves > (uint64_t)plans[y].npre * plans[y].halves;
+    });
+    prf_consts k{};
+    rc = prf_setup(c, k);
+    if (rc) return rc;
+    const uint32_t sw = c->prm.m_bits / 64;
+    // arena: records | work | perm | headers | requests | cores | pre CSR (4 x n) | pre layers |
+    // meta, w_lo, w_hi, salt, rlo, rhi | key | grp, slot | sigma
+    auto al = [](uint64_t b) { return (b + 255) & ~255ull; };
+    const uint64_t off_work = al(n * sizeof(enc_item_rec));
+    const uint64_t off_perm = off_work + al(work.size() * 8);
+    const uint64_t up_bytes = off_perm + al(n * 4);
+    const uint64_t off_hdr = up_bytes;
+    const uint64_t off_req = off_hdr + al(halves * sizeof(enc_half_hdr));
+    const uint64_t off_core = off_req + al(cores * prf_request_bytes());
+    const uint64_t off_csr = off_core + al(cores * 16);
+    const uint64_t off_lay = off_csr + al((uint64_t)n * 32);
+    const uint64_t off_e = off_lay + al(halves * sizeof(pvac_layer));
+    const uint64_t off_key = off_e + al(pe * 48);
+    const uint64_t off_grp = off_key + al(pe * 4);
+    const uint64_t off_sig = off_grp + al(pe * 2);
+    const uint64_t total = off_sig + (with_sigma ? al(pe * sw * 8) : 0);
+    if (const hipError_t ea = c->prf.enc_arena.grow(total, total)) return hip_fail(c, ea, "alloc enc scratch");
+    uint8_t* A = c->prf.enc_arena.get();
+    std::vector<uint8_t> img(up_bytes, 0);
+    std::memcpy(img.data(), recs.data(), n * sizeof(enc_item_rec));
+    std::memcpy(img.data() + off_work, work.data(), work.size() * 8);
+    std::memcpy(img.data() + off_perm, perm.data(), n * 4);
+    if (const hipError_t eu = upload_words(c, A, img.data(), up_bytes)) return hip_fail(c, eu, "enc_items (upload)");
+    pvac_ct_batch pre{};
+    pre.n = n;
+    pre.l_off = (uint64_t*)(A + off_csr);
+    pre.l_cnt = pre.l_off + n;
+    pre.e_off = pre.l_cnt + n;
+    pre.e_cnt = pre.e_off + n;
+    pre.layers = (pvac_layer*)(A + off_lay);
+    pre.meta = (uint64_t*)(A + off_e);
+    pre.w_lo = pre.meta + pe;
+    pre.w_hi = pre.w_lo + pe;
+    pre.sigma = with_sigma ? (uint64_t*)(A + off_sig) : nullptr;
+    pre.sigma_words = with_sigma ? sw : 0;
+    enc_items_args a{};
+    a.n = n;
+    a.n_work = work.size();
+    a.n_halves = halves;
+    a.recs = (const enc_item_rec*)A;
+    a.work = (const uint64_t*)(A + off_work);
+    a.perm = (const uint32_t*)(A + off_perm);
+    a.rnd = rnd;
+    a.powg = c->powg.get();
+    a.canon = c->prm.canon_tag;
+    a.B = c->prm.B;
+    a.hdr = (enc_half_hdr*)(A + off_hdr);
+    a.salt = pre.w_hi + pe;
+    a.rlo = a.salt + pe;
+    a.rhi = a.rlo + pe;
+    a.key = (uint32_t*)(A + off_key);
+    a.grp = A + off_grp;
+    a.slot = a.grp + pe;
+    // timers: the whole sequence, and each launch under its own name (pvac_hip_timing_get)
+    scoped_timer t(c, "enc_items");
+    auto timed = [&](const char* name, auto&& launch) {
+        scoped_timer tk(c, name);
+        return launch();
+    };
+    hipError_t e = timed("enc_items_plan", [&] { return launch_enc_items_plan(a, (prf_request*)(A + off_req), pre, status, c->stream); });
+    if (e == hipSuccess)
+        e = timed("enc_items_prf", [&] { return launch_prf_cores(k, A + off_req, cores, (uint64_t*)(A + off_core), c->stream); });
+    if (e == hipSuccess)
+        e = timed("enc_items_weights", [&] { return launch_enc_items_weights(a, (const uint64_t*)(A + off_core), pre, c->stream); });
+    if (e == hipSuccess && with_sigma)
+        e = timed("enc_items_sigma", [&] { return launch_sigma(c->H, c->prm, pre, a.salt, nullptr, c->num_cus, c->stream); });
+    pvac_ct_batch out = *C;
+    if (!with_sigma) out.sigma = nullptr;
+    if (e == hipSuccess) e = timed("enc_items_finish", [&] { return launch_enc_items_finish(a, pre, out, status, c->stream); });
+    return hip_fail(c, e, "enc_items");
+} catch (...) { return caught(c, "enc_items"); }
+
 int pvac_hip_base_R(pvac_hip_ctx* c, const pvac_ct_batch* X, uint64_t* R_out) try {
     if (!c || !batch_ok(X) || (X->n && !R_out)) return fail(c, PVAC_EINVAL, "base_R: arguments");
     if (!X->n) return PVAC_OK;
