@@ -101,7 +101,7 @@ typedef struct pvac_hip_plan {
     uint64_t n_large;             /* pairs served by the layer-dense path */
     uint64_t n_invalid;           /* reserved, always 0: rejections are per pair, see pvac_hip_ct_mul_status */
     uint32_t max_keys, max_prod, max_na, max_nb, max_buckets, max_layers;  /* launch sizing */
-    uint32_t kind;                /* 1 = mul, 2 = add, 3 = sub, 4 = recrypt, 5 = compact */
+    uint32_t kind;                /* 1 = mul, 2 = add, 3 = sub, 4 = recrypt, 5 = compact, 6 = lincomb */
     uint32_t reserved[5];
 } pvac_hip_plan;
 
@@ -372,6 +372,55 @@ int pvac_hip_ct_add_exec(pvac_hip_ctx* ctx, const pvac_hip_plan* plan, const pva
 /* ct_scale / ct_neg (ops/arithmetic.hpp:33-41): in-place w <- w * s over every edge of the
  * batch (s host scalar). */
 int pvac_hip_ct_scale(pvac_hip_ctx* ctx, pvac_ct_batch* X, uint64_t s_lo, uint64_t s_hi);
+
+/* ct_lincomb: segmented sums of optionally scaled ciphers of one resident batch, bit-exact with the
+ * reference's own fold. Output i, over terms k = seg_off[i] .. seg_off[i + 1] - 1:
+ *     acc = Cipher{};
+ *     for k: t = X[term[k]];
+ *            if (flags[k] & PVAC_TERM_SCALE) t = ct_scale(pk, t, scale[k]);   (arithmetic.hpp:33-37)
+ *            acc = ct_add(pk, acc, t);                       (:12-31, guard_budget + compact_layers)
+ *     C[i] = acc;
+ * An empty segment gives the empty cipher; a one-term segment gives ct_add({}, t), so its unused layers
+ * are dropped. An unscaled term keeps its weight words raw (non-canonical words included); a scaled
+ * one goes through fp_mul whatever the scale (0 keeps its zero-weight edges, a word >= p is used as
+ * given, p - 1 is ct_neg). A cipher may be a term any number of times. Sigma rows are carried when X
+ * and C both have sigma, with equal sigma_words (PVAC_EINVAL when they differ). C's arrays are not X's.
+ * plan: writes C->l_off / C->e_off as exclusive scans of the segments' sums of |X[term].L| and
+ * |X[term].E| (dense CSR capacities; a result is never larger), fills *plan (kind 6, n_small / n_large
+ * = segments on the one-pass / fold route) and synchronises once, or twice when a term takes the
+ * workgroup route (below). Before anything is written to C: PVAC_EINVAL for seg_off[0] != 0, a
+ * decreasing seg_off, seg_off[n] != n_terms or a term index >= X->n (checked on the device, reported
+ * with the plan's statistics); PVAC_ENOSYS for a term above 30000 layers (pvac_hip_ct_add_exec's limit),
+ * a fold-route segment above 30000 layers in all, or a term's or segment's layer or edge count >= 2^31.
+ * exec: writes the rows and exact C->l_cnt / C->e_cnt. It takes this context's latest plan only, with
+ * the X and S it was planned for.
+ * Routes: per term, one pass over its layers and edge headers finds the layers compact_layers keeps
+ * (a lane group and a 64-bit mask for terms of at most 64 layers and 8192 edges: the wave route; one
+ * workgroup with its table in LDS above: the workgroup route). A segment within edge_budget whose terms
+ * are all inside the Cipher contract (every edge's layer_id and every kept PROD parent below its own
+ * |L|) is gathered in one pass: each term compacted on its own lands at its offset, which is what the
+ * fold computes. Any other segment is computed by the literal loop above on pvac_hip_ct_add_plan /
+ * _exec, so a lincomb plan with fold segments invalidates every earlier plan of the context, and its
+ * exec the lincomb plan itself (plan again before another exec).
+ * pvac_hip_ct_lincomb_path_count: since the context was created, out[0] = segments served in one pass,
+ * out[1] = by the fold route, out[2] / out[3] = terms planned on the wave / workgroup route.
+ * pvac_hip_ct_lincomb_status: per segment of the last exec (DEVICE, n u32, stream-ordered copy):
+ * 0 = one pass, 1 = fold because over edge_budget, 2 = fold because a term is out of contract (1 wins
+ * when both hold). */
+#define PVAC_TERM_SCALE 0x1u
+typedef struct pvac_lincomb {
+    uint64_t n, n_terms;
+    const uint64_t* seg_off;   /* DEVICE, n + 1, seg_off[0] = 0, non-decreasing, seg_off[n] = n_terms */
+    const uint64_t* term;      /* DEVICE, n_terms indices into X */
+    const uint64_t* scale;     /* DEVICE, 2 words (lo, hi) per term; NULL = no term is scaled */
+    const uint32_t* flags;     /* DEVICE, per term; NULL with scale != NULL = every term is scaled */
+} pvac_lincomb;
+int pvac_hip_ct_lincomb_plan(pvac_hip_ctx* ctx, const pvac_ct_batch* X, const pvac_lincomb* S, pvac_ct_batch* C,
+                             pvac_hip_plan* plan);
+int pvac_hip_ct_lincomb_exec(pvac_hip_ctx* ctx, const pvac_hip_plan* plan, const pvac_ct_batch* X, const pvac_lincomb* S,
+                             pvac_ct_batch* C);
+int pvac_hip_ct_lincomb_path_count(pvac_hip_ctx* ctx, uint64_t out[4]);
+int pvac_hip_ct_lincomb_status(pvac_hip_ctx* ctx, uint32_t* out, size_t n);
 
 /* sigma_from_H for every edge of a batch (crypto/matrix.hpp:267-303): sigma of edge slot e
  * from its layer's (ztag, nonce), idx, ch and salts[e]. Requires H (set_H / gen_H). */

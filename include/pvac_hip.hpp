@@ -16,7 +16,9 @@
 //   pvac::enc_value(pk, sk, v) (ops/encrypt.hpp:289)  -> pvac_hip::enc_value<Cipher>(pk, sk, v)
 //   pvac::dec_value(pk, sk, C) (ops/decrypt.hpp:62)  -> pvac_hip::dec_value(pk, sk, C)
 //   saveCts / loadCts          (tests/add.cpp:22-155) -> pvac_hip::save_cts_bytes / load_cts_bytes
-// plus batched forms (std::vector of pairs in, std::vector out) that keep one launch per batch.
+// plus batched forms (std::vector of pairs in, std::vector out) that keep one launch per batch, and
+// ct_sum / ct_lincomb / ct_lincomb_batch: the fold acc = ct_add(pk, acc, [ct_scale] x_k) of any number
+// of ciphers as one call (pvac_hip_ct_lincomb_plan / _exec).
 // enc/dec also read pk.H_digest, pk.powg_B, pk.prm.lpn_* and the SecKey's prf_k / lpn_s_bits.
 //
 // Randomness: like the reference (core/random.hpp:40-110), nonces (2 words per new product
@@ -390,6 +392,43 @@ std::vector<CipherT> from_view(const pvac_ct_batch& v, uint32_t m_bits, hipStrea
     return convert_host<CipherT>(c, n, m_bits, sig);
 }
 
+// The ragged term lists of a ct_lincomb call as the C ABI takes them (pvac_lincomb, host side):
+// seg_off has one entry more than there are outputs, scale 2 words (lo, hi) per term or none, flags
+// one word per term or none (none with scales: every term is scaled).
+struct lincomb_lists {
+    std::vector<uint64_t> seg_off, term, scale;
+    std::vector<uint32_t> flags;
+};
+
+// Checks a call against a pool of n_x ciphers and flattens the scales: seg_off starts at 0, does not
+// decrease and ends at term.size() (an empty seg_off is no output at all); every term is below n_x;
+// scales and flags are empty or one per term, flags only with scales. Pure host arithmetic
+// (tests/cpp/lincomb_flatten_check.cpp).
+template <class FpT>
+lincomb_lists flatten_lincomb(size_t n_x, const std::vector<uint64_t>& seg_off, const std::vector<uint64_t>& term,
+                              const std::vector<FpT>& scales, const std::vector<uint32_t>& flags) {
+    lincomb_lists s;
+    s.seg_off = seg_off;
+    if (s.seg_off.empty()) s.seg_off.push_back(0);
+    if (s.seg_off.front() != 0 || s.seg_off.back() != term.size())
+        throw Error(PVAC_EINVAL, "ct_lincomb: seg_off must run from 0 to the number of terms");
+    for (size_t i = 1; i < s.seg_off.size(); ++i)
+        if (s.seg_off[i] < s.seg_off[i - 1]) throw Error(PVAC_EINVAL, "ct_lincomb: seg_off decreases");
+    for (const uint64_t t : term)
+        if (t >= n_x) throw Error(PVAC_EINVAL, "ct_lincomb: a term index beyond the pool");
+    if ((!scales.empty() && scales.size() != term.size()) || (!flags.empty() && flags.size() != term.size()) ||
+        (scales.empty() && !flags.empty()))
+        throw Error(PVAC_EINVAL, "ct_lincomb: scales / flags are one per term (flags only with scales)");
+    s.term = term;
+    s.scale.reserve(2 * scales.size());
+    for (const FpT& f : scales) {
+        s.scale.push_back(f.lo);
+        s.scale.push_back(f.hi);
+    }
+    s.flags = flags;
+    return s;
+}
+
 }  // namespace detail
 
 // One device context per (device, canon_tag); owns the device copy of pk.H for sigma.
@@ -711,6 +750,44 @@ public:
         vc.n = n;
         check(pvac_hip_ct_add_exec(ctx_, &plan, &va, &vb, negate_b ? 1 : 0, &vc));
         return detail::from_device<CipherT>(c, n, plan.total_layer_slots, plan.total_edge_slots, prm_.m_bits, true,
+                                            stream_);
+    }
+
+    // ct_lincomb (pvac_hip_ct_lincomb_plan / _exec): output i is the reference's fold over the terms
+    // S.term[S.seg_off[i] .. S.seg_off[i + 1]) of the pool X. with_sigma = false computes weights only
+    // (results keep empty BitVecs, as ct_mul's weights-only results do).
+    template <class CipherT>
+    std::vector<CipherT> ct_lincomb(const std::vector<const CipherT*>& X, const detail::lincomb_lists& S, bool with_sigma) {
+        const size_t n = S.seg_off.size() - 1;
+        if (!n) return {};
+        detail::batch x, c;
+        detail::to_host(X, sigma_words(), with_sigma, x);
+        detail::upload(x, stream_, with_sigma);
+        detail::dev_array<uint64_t> d_so(S.seg_off.size()), d_tm(S.term.size()), d_sc(S.scale.size());
+        detail::dev_array<uint32_t> d_fl(S.flags.size());
+        d_so.upload(S.seg_off.data(), S.seg_off.size(), stream_);
+        d_tm.upload(S.term.data(), S.term.size(), stream_);
+        d_sc.upload(S.scale.data(), S.scale.size(), stream_);
+        d_fl.upload(S.flags.data(), S.flags.size(), stream_);
+        pvac_lincomb s{};
+        s.n = n;
+        s.n_terms = S.term.size();
+        s.seg_off = d_so.p;
+        s.term = d_tm.p;
+        s.scale = S.scale.empty() ? nullptr : d_sc.p;
+        s.flags = S.flags.empty() ? nullptr : d_fl.p;
+        const pvac_ct_batch vx = x.view(with_sigma);
+        c.d_l_off.alloc(n); c.d_l_cnt.alloc(n); c.d_e_off.alloc(n); c.d_e_cnt.alloc(n);
+        pvac_ct_batch vc{};
+        vc.l_off = c.d_l_off.p; vc.l_cnt = c.d_l_cnt.p; vc.e_off = c.d_e_off.p; vc.e_cnt = c.d_e_cnt.p;
+        vc.sigma_words = sigma_words();
+        pvac_hip_plan plan{};
+        check(pvac_hip_ct_lincomb_plan(ctx_, &vx, &s, &vc, &plan));
+        detail::alloc_out(c, n, plan.total_layer_slots, plan.total_edge_slots, sigma_words(), with_sigma);
+        vc = c.view(with_sigma);
+        vc.n = n;
+        check(pvac_hip_ct_lincomb_exec(ctx_, &plan, &vx, &s, &vc));
+        return detail::from_device<CipherT>(c, n, plan.total_layer_slots, plan.total_edge_slots, prm_.m_bits, with_sigma,
                                             stream_);
     }
 
@@ -1387,6 +1464,38 @@ std::vector<CipherT> ct_add_batch(const PubKeyT& pk, const std::vector<CipherT>&
     for (auto& x : A) a.push_back(&x);
     for (auto& x : B) b.push_back(&x);
     return engine_for(pk).ct_add(a, b, negate_b);
+}
+
+// ---- sums of many ciphers: the fold acc = {}; acc = ct_add(pk, acc, [ct_scale(pk, x_k, s_k)]) in one call
+// (sum_sq = ct_add(pk, sum_sq, ...) loops and ct_add / ct_sub / ct_scale polynomials of the reference's
+// examples). Bit-exact with that fold, guard_budget and compact_layers included. INTEGRATION.md says
+// when to prefer it over ct_add_batch.
+template <class PubKeyT, class CipherT, class FpT>
+std::vector<CipherT> ct_lincomb_batch(const PubKeyT& pk, const std::vector<CipherT>& X, const std::vector<uint64_t>& seg_off,
+                                      const std::vector<uint64_t>& term, const std::vector<FpT>& scales,
+                                      const std::vector<uint32_t>& flags = {}, bool with_sigma = true) {
+    std::vector<const CipherT*> x;
+    for (auto& c : X) x.push_back(&c);
+    return engine_for(pk).ct_lincomb(x, detail::flatten_lincomb(X.size(), seg_off, term, scales, flags), with_sigma);
+}
+
+// cs[0] + cs[1] + ... (an empty vector gives the empty cipher)
+template <class PubKeyT, class CipherT>
+CipherT ct_sum(const PubKeyT& pk, const std::vector<CipherT>& cs, bool with_sigma = true) {
+    using FpT = std::decay_t<decltype(cs[0].E[0].w)>;
+    std::vector<uint64_t> term(cs.size());
+    for (size_t k = 0; k < cs.size(); ++k) term[k] = k;
+    return ct_lincomb_batch(pk, cs, {0, (uint64_t)cs.size()}, term, std::vector<FpT>{}, {}, with_sigma)[0];
+}
+
+// scales[0] cs[0] + scales[1] cs[1] + ...: every term goes through ct_scale, whatever its scale
+template <class PubKeyT, class CipherT, class FpT>
+CipherT ct_lincomb(const PubKeyT& pk, const std::vector<CipherT>& cs, const std::vector<FpT>& scales, bool with_sigma = true) {
+    if (scales.size() != cs.size()) throw Error(PVAC_EINVAL, "ct_lincomb: one scale per cipher");
+    std::vector<uint64_t> term(cs.size());
+    for (size_t k = 0; k < cs.size(); ++k) term[k] = k;
+    // no scales at all would mean "unscaled": an empty sum has nothing to scale either way
+    return ct_lincomb_batch(pk, cs, {0, (uint64_t)cs.size()}, term, scales, {}, with_sigma)[0];
 }
 
 // ---- ct_recrypt and its parts (ops/recrypt.hpp, ops/encrypt.hpp:29-104, crypto/matrix.hpp:306-310)

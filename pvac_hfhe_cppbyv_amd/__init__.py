@@ -85,6 +85,14 @@ class Plan(C.Structure):
                 ("kind", C.c_uint32), ("reserved", C.c_uint32 * 5)]
 
 
+class Lincomb(C.Structure):
+    """pvac_lincomb: the ragged term lists of a ct_lincomb call (device pointers)."""
+    _fields_ = [("n", C.c_uint64), ("n_terms", C.c_uint64), ("seg_off", C.c_void_p), ("term", C.c_void_p),
+                ("scale", C.c_void_p), ("flags", C.c_void_p)]
+
+
+TERM_SCALE = 0x1
+
 FILL_NONCES_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p)
 ON_CHUNK_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(CtBatch), C.c_void_p)
 # pvac_chain_step_fn(user, step, first_input, A, X, C, dev_words, n_words, stream): nonces_at / after_step / salts_at
@@ -150,6 +158,12 @@ def load_library(path: str = _LIB_PATH) -> C.CDLL:
         "pvac_hip_ct_add_exec": ([vp, C.POINTER(Plan), C.POINTER(CtBatch), C.POINTER(CtBatch), i32,
                                   C.POINTER(CtBatch)], i32),
         "pvac_hip_ct_scale": ([vp, C.POINTER(CtBatch), u64, u64], i32),
+        "pvac_hip_ct_lincomb_plan": ([vp, C.POINTER(CtBatch), C.POINTER(Lincomb), C.POINTER(CtBatch),
+                                      C.POINTER(Plan)], i32),
+        "pvac_hip_ct_lincomb_exec": ([vp, C.POINTER(Plan), C.POINTER(CtBatch), C.POINTER(Lincomb),
+                                      C.POINTER(CtBatch)], i32),
+        "pvac_hip_ct_lincomb_path_count": ([vp, C.POINTER(u64)], i32),
+        "pvac_hip_ct_lincomb_status": ([vp, vp, C.c_size_t], i32),
         "pvac_hip_sigma_batch": ([vp, C.POINTER(CtBatch), vp], i32),
         "pvac_hip_ctx_set_ubk": ([vp, vp, u32], i32),
         "pvac_hip_sigma_popcount": ([vp, C.POINTER(CtBatch), vp], i32),
@@ -740,6 +754,97 @@ class Engine:
         self._check(self.lib.pvac_hip_ct_add_exec(self.ctx, C.byref(plan), C.byref(sa), C.byref(sb), int(negate),
                                                   C.byref(sc)))
         return C_
+
+    # ---- ct_lincomb: segmented sums of optionally scaled ciphers (pvac_hip_ct_lincomb_plan / _exec)
+    def _index_tensor(self, a, dtype=np.uint64):
+        """A numpy / torch / list index array as a device tensor of `dtype` words (at least one)."""
+        torch = self.torch
+        if isinstance(a, torch.Tensor):
+            want = torch.int64 if dtype == np.uint64 else torch.int32
+            t = a.to(device=self.device, dtype=want).contiguous().reshape(-1)
+            return t if t.numel() else torch.zeros(1, dtype=want, device=self.device)
+        h = np.ascontiguousarray(np.asarray(a, dtype=dtype).reshape(-1))
+        if not len(h):
+            h = np.zeros(1, dtype)
+        return torch.from_numpy(h.view(np.int64 if dtype == np.uint64 else np.int32)).to(self.device)
+
+    def ct_lincomb(self, X: DeviceBatch, seg_off, term, scale=None, flags=None, sigma=False) -> DeviceBatch:
+        """Output i = the reference's fold acc = ct_add(acc, [ct_scale] X[term[k]]) over terms
+        k = seg_off[i] .. seg_off[i + 1] - 1. seg_off: n + 1 offsets; term: indices into X; scale: one Fp
+        per term, as Python ints or an (n_terms, 2) u64 array of (lo, hi) words (None: nothing is scaled);
+        flags: per term, TERM_SCALE where the scale applies (None with a scale: every term). Index
+        arrays may be numpy or torch. sigma=True carries X's sigma rows."""
+        C_, plan, call = self.ct_lincomb_plan(X, seg_off, term, scale, flags, sigma)
+        return self.ct_lincomb_exec(C_, plan, call)
+
+    def ct_lincomb_plan(self, X: DeviceBatch, seg_off, term, scale=None, flags=None, sigma=False, C_=None):
+        """The plan half of ct_lincomb: (C with its offsets and row arrays sized, plan, call), `call`
+        holding the argument structures (and the tensors behind them) for ct_lincomb_exec. C_: a batch
+        to plan into instead of a new one (its row arrays are kept when they are large enough)."""
+        torch = self.torch
+        so = self._index_tensor(seg_off)
+        n_terms = len(term)
+        n = max(len(seg_off) - 1, 0)
+        tm = self._index_tensor(term)
+        sc = fl = None
+        if scale is not None:
+            if not isinstance(scale, (np.ndarray, torch.Tensor)):
+                words = lambda s: (int(s[0]), int(s[1])) if isinstance(s, (tuple, list, np.ndarray)) else \
+                    (int(s) & ((1 << 64) - 1), (int(s) >> 64) & ((1 << 64) - 1))
+                scale = np.array([words(s) for s in scale], np.uint64).reshape(-1, 2)
+            sc = self._index_tensor(scale)
+            if flags is not None:
+                fl = self._index_tensor(flags, np.uint32)
+        S = Lincomb(n, n_terms, so.data_ptr(), tm.data_ptr(), sc.data_ptr() if sc is not None else None,
+                    fl.data_ptr() if fl is not None else None)
+        if sigma and X.sigma is None:
+            raise PvacError("ct_lincomb: sigma=True needs a batch with sigma")
+        z = lambda: torch.zeros(max(n, 1), dtype=torch.int64, device=self.device)
+        if C_ is None:
+            C_ = DeviceBatch(n, z(), z(), None, z(), z(), None, None, None)
+        plan = Plan()
+        sx, sc_ = X.struct(), C_.struct()
+        if not sigma:
+            sx.sigma = None
+        self._check(self.lib.pvac_hip_ct_lincomb_plan(self.ctx, C.byref(sx), C.byref(S), C.byref(sc_), C.byref(plan)))
+        C_.n = n
+        e, nl = max(plan.total_edge_slots, 1), max(plan.total_layer_slots, 1)
+        if C_.layers is None or C_.layers.shape[0] < nl:
+            C_.layers = torch.empty((nl, 5), dtype=torch.int64, device=self.device)
+        for f in ("meta", "w_lo", "w_hi"):
+            if getattr(C_, f) is None or getattr(C_, f).shape[0] < e:
+                setattr(C_, f, torch.empty(e, dtype=torch.int64, device=self.device))
+        if sigma and (C_.sigma is None or C_.sigma.shape[0] < e):
+            C_.sigma = torch.empty((e, X.sigma.shape[1]), dtype=torch.int64, device=self.device)
+        if not sigma:
+            C_.sigma = None
+        return C_, plan, (sx, S, (X, so, tm, sc, fl))
+
+    def ct_lincomb_exec(self, C_: DeviceBatch, plan, call) -> DeviceBatch:
+        sx, S, _keep = call
+        sc_ = C_.struct()
+        self._check(self.lib.pvac_hip_ct_lincomb_exec(self.ctx, C.byref(plan), C.byref(sx), C.byref(S), C.byref(sc_)))
+        return C_
+
+    def ct_sum(self, X: DeviceBatch, seg_off, term=None, sigma=False) -> DeviceBatch:
+        """The unscaled ct_lincomb; term=None sums consecutive ciphers: output i = X[seg_off[i]] + ... ."""
+        if term is None:
+            so = seg_off.cpu().numpy() if isinstance(seg_off, self.torch.Tensor) else np.asarray(seg_off)
+            term = np.arange(int(so[-1]) if len(so) else 0, dtype=np.uint64)
+        return self.ct_lincomb(X, seg_off, term, sigma=sigma)
+
+    def ct_lincomb_path_counts(self):
+        """Since the context was created: segments served in one pass / by the fold route, terms planned
+        on the wave / workgroup route."""
+        v = (C.c_uint64 * 4)()
+        self._check(self.lib.pvac_hip_ct_lincomb_path_count(self.ctx, v))
+        return {"one_pass": int(v[0]), "fold": int(v[1]), "wave_terms": int(v[2]), "wg_terms": int(v[3])}
+
+    def ct_lincomb_status(self, n):
+        """Per segment of the last ct_lincomb: 0 one pass, 1 fold (over edge_budget), 2 fold (contract)."""
+        out = self.torch.zeros(max(n, 1), dtype=self.torch.int32, device=self.device)
+        self._check(self.lib.pvac_hip_ct_lincomb_status(self.ctx, C.c_void_p(out.data_ptr()), n))
+        return out[:n].cpu().numpy().view(np.uint32)
 
     def ct_scale(self, X: DeviceBatch, s: int):
         sx = X.struct()

@@ -505,4 +505,56 @@ hipError_t launch_grp_build(fastmod64 nbm, uint32_t Bm, uint64_t S, uint32_t hbi
 hipError_t launch_ct_add(const pvac_ct_batch& A, const pvac_ct_batch& B, pvac_ct_batch& C, int negate_b,
                          uint32_t max_layers, const uint8_t* pair_class, hipStream_t st);
 
+// ---- ct_lincomb (k_lincomb.hip): segmented sums of optionally scaled ciphers, the work unit the term.
+// Terms of at most kLinWaveLayers layers and kLinWaveEdges edges are closed by a lane group (the
+// wave route: a 64-bit keep mask), the others by one workgroup each (a remap table in scratch).
+constexpr uint32_t kLinWaveLayers = 64;
+constexpr uint32_t kLinWaveEdges = 8192;
+constexpr uint32_t kLinMaxLayers = 30000;          // per term: pvac_hip_ct_add_exec's limit
+constexpr uint64_t kLinKeptMask = (1ull << 40) - 1;   // kraw / sK: kept layers below bit 40, flagged terms above
+// segment classes (lincomb_args::cls, pvac_hip_ct_lincomb_status)
+enum : uint32_t { LIN_ONE_PASS = 0, LIN_FOLD_BUDGET = 1, LIN_FOLD_CONTRACT = 2 };
+struct lincomb_args {
+    pvac_ct_batch X, C;
+    uint64_t n, n_terms;
+    const uint64_t* seg_off;   // [n + 1]
+    const uint64_t* term;      // [n_terms]
+    const uint64_t* scale;     // nullable, 2 words per term
+    const uint32_t* flags;     // nullable
+    // context-owned per-term scratch, n_terms + 1 words each (the last one closes the scans)
+    uint64_t* sL;              // |X[term].L|, then its exclusive scan: C.l_off[i] = sL[seg_off[i]]
+    uint64_t* sE;              // |X[term].E|, then its exclusive scan: term k's edges land at sE[k]
+    uint64_t* kraw;            // kept layers | (out of contract ? 1 : 0) << 40
+    uint64_t* sK;              // exclusive scan of kraw
+    uint64_t* mask;            // wave route: the keep mask
+    uint32_t* tseg;            // [n_terms] the term's segment
+    uint8_t* troute;           // [n_terms] 0 = wave route, 1 = workgroup route
+    uint64_t* wg_ids;          // [n_terms] the workgroup route's terms (plan_stats::n_small of them)
+    uint32_t* remap;           // workgroup route: new layer id (0xFFFFFFFF = dropped) at sL[k] + layer
+    uint32_t* cls;             // [n] segment class
+    uint64_t* fold_ids;        // [n] the fold route's segments (plan_stats::n_large of them)
+    // the copy pass's tiles: the term that holds the first layer slot / edge of tile b (kLinLayerTile
+    // input layer slots, kLinEdgeTile output edges per workgroup), and n_terms - 1 at the end
+    uint32_t* tile_l;
+    uint32_t* tile_e;
+    plan_stats* stats;
+    uint64_t edge_budget;
+};
+constexpr uint32_t kLinLayerTile = 256;
+constexpr uint32_t kLinEdgeTile = 1024;
+// plan_stats as the lincomb plan uses it: n_small = workgroup-route terms, n_large = fold segments,
+// n_invalid = bad seg_off entries and term indices, max_layers / max_na = largest term |L| / |E|,
+// max_prod / max_nb = largest segment layer / edge total, max_buckets = largest fold segment layer
+// total (all saturated at 2^32 - 1).
+// 1. per term: index check, counts, segment, keep mask of the wave route; seg_off's own checks
+hipError_t launch_lincomb_plan(const lincomb_args& a, hipStream_t st);
+// 2. (after the scans of sL / sE) the workgroup route's n_wg terms: keep table in LDS -> remap, kraw
+hipError_t launch_lincomb_plan_wg(const lincomb_args& a, uint64_t n_wg, uint32_t max_layers, hipStream_t st);
+// 3. (after the scan of kraw into sK) per segment: class, fold list, segment maxima
+hipError_t launch_lincomb_classify(const lincomb_args& a, hipStream_t st);
+// 4. C.l_off / C.e_off and the copy pass's tile tables
+hipError_t launch_lincomb_layout(const lincomb_args& a, uint64_t total_layers, uint64_t total_edges, hipStream_t st);
+// exec: layers, edges (and sigma rows) of every one-pass segment, then C.l_cnt / C.e_cnt
+hipError_t launch_lincomb_copy(const lincomb_args& a, uint64_t total_layers, uint64_t total_edges, hipStream_t st);
+
 }  // namespace pvhip

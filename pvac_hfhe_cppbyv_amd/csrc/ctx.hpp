@@ -201,6 +201,21 @@ struct pvac_hip_ctx {
             pvhip::dev_buf<uint64_t> meta, w_lo, w_hi, sigma;
         } buf[2];
     } recrypt;
+    struct {   // ct_lincomb (rt_lincomb.cpp, k_lincomb.hip)
+        pvhip::dev_buf<uint64_t> terms;              // the latest plan's five per-term arrays, n_terms + 1 words each
+        pvhip::dev_buf<uint32_t> tseg, remap, cls, tile_l, tile_e;
+        pvhip::dev_buf<uint8_t> troute;
+        pvhip::dev_buf<uint64_t> wg_ids, fold_ids;
+        uint64_t n = 0, n_terms = 0, n_wg = 0, n_fold = 0;   // ... and its shape
+        uint64_t status_n = 0;                       // segments of the last exec (cls holds their status)
+        uint64_t path[4] = {};                       // segments one-pass / fold, terms wave / workgroup route
+        struct set {                                 // the fold route's accumulator, ping-pong
+            pvhip::dev_buf<pvac_layer> layers;
+            pvhip::dev_buf<uint64_t> meta, w_lo, w_hi, sigma;
+        } acc[2];
+        pvhip::dev_buf<uint64_t> sw_lo, sw_hi;       // a scaled term's weights
+        pvhip::dev_buf<uint64_t> words;              // zero offsets, the accumulators' counts, a plan's offsets
+    } lincomb;
     struct {   // check_mul_gsum (rt_util.cpp)
         pvhip::dev_buf<unsigned int> buf;        // 4 layer maxima, then a u64 failure count
         pvhip::dev_buf<uint8_t> scratch;         // layer tables beyond LDS (global slabs)
