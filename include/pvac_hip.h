@@ -487,6 +487,53 @@ int pvac_hip_ct_recrypt_exec(pvac_hip_ctx* ctx, const pvac_hip_plan* plan, const
  * context's stream; not synchronous. */
 int pvac_hip_commit_ct(pvac_hip_ctx* ctx, const pvac_ct_batch* X, uint8_t* digests);
 
+/* ---------------------------------------------------------------- metrics (utils/metrics.hpp)
+ * The per-cipher readers of sigma and weights, computed where the ciphers are.
+ *
+ * pvac_hip_sigma_bytehist: hist (DEVICE, 256 * X->n u64): hist[256 i + b] = the number of bytes equal
+ * to b among the 8 mw bytes of each of cipher i's sigma rows e_off[i] .. e_off[i] + e_cnt[i] - 1,
+ * mw = ceil(m_bits / 64): a row contributes its first mw words (every byte of them, the bits past
+ * m_bits in the last word included), the row stride is X->sigma_words. All 256 entries of every cipher
+ * are written (an empty cipher gets zeros; the caller zeroes nothing); slots past e_cnt of a
+ * capacity-padded batch are never read; n = 0 launches nothing. PVAC_EINVAL when X->sigma is null with
+ * n > 0 or sigma_words * 64 < m_bits (pvac_hip_sigma_popcount's rules). Enqueued on the context's
+ * stream; not synchronous. Timing label "sigma_bytehist".
+ * Relation to the reference: sigma_shannon(C) (metrics.hpp:43-68) = - sum over b = 0 .. 255 with
+ * freq[b] > 0 of p_b log2 p_b, p_b = (double)freq[b] / total, freq = hist's row of C and total its
+ * sum. The reference counts in int, so it is undefined from 2^31 bytes per cipher (2,097,152 rows of
+ * 1 KiB); the counts here are exact u64 at any size. The logarithms stay on the host (256 per cipher,
+ * in the reference's floating-point order: pvac_hip.hpp's sigma_shannon).
+ * Identities: sum over b of hist[256 i + b] = 8 mw e_cnt[i], and sum over b of popcount(b)
+ * hist[256 i + b] = ones[i] of pvac_hip_sigma_popcount.
+ *
+ * pvac_hip_layer_gsum: gsum (DEVICE, 2 words (lo, hi) per layer SLOT of X, parallel to X->layers like
+ * pvac_hip_base_R's output): for l < l_cnt[i], slot l_off[i] + l receives agg_layer_gsum(pk, X_i, l)
+ * (metrics.hpp:70-86) = the sum over X_i's edges of layer l of +/- fp_mul(w, powg_B[idx]), + for SGN_P;
+ * other slots are not written. An edge whose layer_id >= l_cnt[i] is ignored (the reference's loop
+ * never asks for it). status (DEVICE, n u32, nullable), written for every cipher: 0 ok; 2 an edge of
+ * that cipher has idx >= B (the reference reads past powg_B): its sums are unspecified, every write
+ * stays in bounds and its neighbours are unaffected. Needs pvac_hip_ctx_set_powg (PVAC_EINVAL
+ * without, as pvac_hip_check_mul_gsum). Contract (that of pvac_hip_check_mul_gsum's sums): each term
+ * is the bit-exact fp_mul; the result is the exact residue mod p of the signed sum of the terms, which
+ * equals the reference's fp_add / fp_sub chain whenever the terms are canonical (every cipher inside
+ * the Cipher contract). There is no edge-count limit: a cipher of 2^21 edges or more (where the
+ * checker's 43/42/42-bit limb sums could pass 2^64) is summed in pieces of 2^20 edges, each folded
+ * mod p before the pieces are combined. PVAC_ENOSYS for a cipher of 2^28 layers or more. Synchronises
+ * once (the size pass that picks the launch's LDS and scratch), then the kernel is enqueued. Timing
+ * label "layer_gsum".
+ * Routes, per cipher: at most 16 layers and 4096 edges: one wave of a workgroup that serves four
+ * consecutive ciphers (the wave route); up to 3200 layers (48 bytes of table per layer in LDS) and
+ * fewer than 2^21 edges: one workgroup (the workgroup route); 2^21 edges or more (pieces) or more
+ * layers than LDS holds (the table in a slab of context scratch): the large route.
+ *
+ * pvac_hip_metrics_path_count, since the context was created: out[0] / out[1] = sigma_bytehist calls
+ * (n > 0) served by the 16-byte-load path / the 8-byte path (a row stride different from mw, odd mw,
+ * or a base pointer not 16-byte aligned); out[2] / out[3] / out[4] = ciphers pvac_hip_layer_gsum
+ * served on the wave / workgroup / large route. */
+int pvac_hip_sigma_bytehist(pvac_hip_ctx* ctx, const pvac_ct_batch* X, uint64_t* hist);
+int pvac_hip_layer_gsum(pvac_hip_ctx* ctx, const pvac_ct_batch* X, uint64_t* gsum, uint32_t* status);
+int pvac_hip_metrics_path_count(pvac_hip_ctx* ctx, uint64_t out[5]);
+
 /* ---------------------------------------------------------------- synthetic inputs / checks
  * Fresh-shaped cipher generator used by bench.py (SURVEY §8(d) cfg 3 generator): per cipher
  * 2 BASE layers (random ztag/nonce), per layer `edges_per_layer` distinct (idx, ch), uniform

@@ -39,12 +39,15 @@
 #include <algorithm>
 #include <array>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <exception>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <functional>
+#include <iomanip>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -1203,6 +1206,96 @@ public:
         return out;
     }
 
+    // pk.powg_B alone: agg_layer_gsum reads no secret key (ensure_keys uploads the same table)
+    template <class PubKeyT>
+    void ensure_powg(const PubKeyT& pk) {
+        if (keys_ready_ || powg_ready_) return;
+        std::vector<uint64_t> pg(2 * pk.powg_B.size());
+        for (size_t i = 0; i < pk.powg_B.size(); ++i) { pg[2 * i] = pk.powg_B[i].lo; pg[2 * i + 1] = pk.powg_B[i].hi; }
+        check(pvac_hip_ctx_set_powg(ctx_, pg.data(), (uint32_t)pk.powg_B.size()));
+        powg_ready_ = true;
+    }
+
+    // The reference's entropy expression (utils/metrics.hpp:58-67) on 256 exact byte counts: bins in
+    // order 0 .. 255, p = (double)freq / total, H -= p * log2(p) over the non-empty bins.
+    static double shannon_of_counts(const uint64_t* freq) {
+        uint64_t total = 0;
+        for (int b = 0; b < 256; ++b) total += freq[b];
+        if (total == 0) return 0.0;
+        double H = 0.0;
+        for (int b = 0; b < 256; ++b) {
+            if (freq[b] > 0) {
+                const double p = (double)freq[b] / total;
+                H -= p * std::log2(p);
+            }
+        }
+        return H;
+    }
+
+    // sigma_shannon (utils/metrics.hpp:43-68) per cipher: the exact byte counts from the device
+    // (pvac_hip_sigma_bytehist), the 256 logarithms on the host. 0.0 for an empty cipher and for one
+    // whose edges carry no sigma words (the reference's total == 0). The reference counts each edge's
+    // own e.s.w; here a cipher has every edge at ceil(m_bits / 64) words or every edge at none, and any
+    // other width throws: there is no host fallback.
+    template <class CipherT>
+    std::vector<double> sigma_shannon(const std::vector<const CipherT*>& cs) {
+        const size_t n = cs.size();
+        std::vector<double> H(n, 0.0);
+        std::vector<size_t> ids;
+        for (size_t i = 0; i < n; ++i) {
+            if (cs[i]->E.empty()) continue;
+            const size_t nw = cs[i]->E[0].s.w.size();
+            for (const auto& e : cs[i]->E)
+                if (e.s.w.size() != nw) throw Error(PVAC_EINVAL, "sigma_shannon: a cipher's edges disagree on sigma words");
+            if (nw != 0 && nw != (size_t)sigma_words())
+                throw Error(PVAC_EINVAL, "sigma_shannon: sigma rows are neither empty nor ceil(m_bits / 64) words");
+            if (nw) ids.push_back(i);
+        }
+        const size_t m = ids.size();
+        if (!m) return H;
+        std::vector<const CipherT*> sub(m);
+        for (size_t j = 0; j < m; ++j) sub[j] = cs[ids[j]];
+        detail::batch x;
+        detail::to_host(sub, sigma_words(), true, x);
+        detail::upload(x, stream_, true);
+        pvac_ct_batch vx = x.view(true);
+        detail::dev_array<uint64_t> hist(256 * m);
+        check(pvac_hip_sigma_bytehist(ctx_, &vx, hist.p));
+        const detail::hvec<uint64_t> h = detail::d2h_u64(hist.p, 256 * m, stream_);
+        for (size_t j = 0; j < m; ++j) H[ids[j]] = shannon_of_counts(&h[256 * j]);
+        return H;
+    }
+
+    // agg_layer_gsum (utils/metrics.hpp:70-86) of every layer of every cipher (pvac_hip_layer_gsum).
+    // An edge with idx >= B (the reference reads past pk.powg_B) throws.
+    template <class PubKeyT, class CipherT, class FpT>
+    std::vector<std::vector<FpT>> layer_gsums(const PubKeyT& pk, const std::vector<const CipherT*>& cs) {
+        const size_t n = cs.size();
+        std::vector<std::vector<FpT>> out(n);
+        if (!n) return out;
+        ensure_powg(pk);
+        detail::batch x;
+        detail::to_host(cs, sigma_words(), false, x);
+        detail::upload(x, stream_, false);
+        pvac_ct_batch vx = x.view(false);
+        const size_t slots = x.layers.size();
+        detail::dev_array<uint64_t> g(2 * (slots ? slots : 1));
+        detail::dev_array<uint32_t> st(n);
+        check(pvac_hip_layer_gsum(ctx_, &vx, g.p, st.p));
+        std::vector<uint32_t> s(n);
+        st.download(s.data(), n, stream_);
+        const detail::hvec<uint64_t> w = detail::d2h_u64(g.p, 2 * slots, stream_);
+        for (size_t i = 0; i < n; ++i) {
+            if (s[i]) throw Error(PVAC_EINVAL, "agg_layer_gsum: an edge's idx is out of range");
+            out[i].resize(cs[i]->L.size());
+            for (size_t l = 0; l < out[i].size(); ++l) {
+                out[i][l].lo = w[2 * (x.l_off[i] + l)];
+                out[i][l].hi = w[2 * (x.l_off[i] + l) + 1];
+            }
+        }
+        return out;
+    }
+
 private:
     void check(int rc) {
         if (rc) throw Error(rc, std::string("pvac_hip: ") + pvac_hip_last_error(ctx_));
@@ -1268,6 +1361,7 @@ private:
     bool h_ready_ = false;
     bool keys_ready_ = false;
     bool ubk_ready_ = false;
+    bool powg_ready_ = false;
     Phases phases_;
     detail::pinned_batch mul_a_, mul_b_, mul_c_, mul_p_;
     detail::dev_array<uint64_t> mul_nonces_, mul_salts_;
@@ -1545,6 +1639,68 @@ std::vector<std::array<uint8_t, 32>> commit_ct_batch(const PubKeyT& pk, const st
     std::vector<const CipherT*> p;
     for (auto& x : cs) p.push_back(&x);
     return engine_for(pk).commit_ct(pk, p);
+}
+
+// ---- metrics (utils/metrics.hpp) --------------------------------------------------------------
+// sigma_shannon (metrics.hpp:43-68): the reference's signature has no PubKey; the engine is found by it
+template <class PubKeyT, class CipherT>
+double sigma_shannon(const PubKeyT& pk, const CipherT& C) {
+    return engine_for(pk).sigma_shannon(std::vector<const CipherT*>{&C})[0];
+}
+
+template <class PubKeyT, class CipherT>
+std::vector<double> sigma_shannon_batch(const PubKeyT& pk, const std::vector<CipherT>& cs) {
+    std::vector<const CipherT*> p;
+    for (auto& x : cs) p.push_back(&x);
+    return engine_for(pk).sigma_shannon(p);
+}
+
+// every layer's agg_layer_gsum (metrics.hpp:70-86) of every cipher: out[i][l] = agg_layer_gsum(pk, cs[i], l)
+template <class FpT, class PubKeyT, class CipherT>
+std::vector<std::vector<FpT>> layer_gsums_batch(const PubKeyT& pk, const std::vector<CipherT>& cs) {
+    std::vector<const CipherT*> p;
+    for (auto& x : cs) p.push_back(&x);
+    return engine_for(pk).template layer_gsums<PubKeyT, CipherT, FpT>(pk, p);
+}
+
+// agg_layer_gsum(pk, X, lid): a layer id no layer of X carries sums no edge the batched form reports,
+// so it gives what the reference's loop gives for it when no edge names it: fp_from_u64(0)
+template <class FpT, class PubKeyT, class CipherT>
+FpT agg_layer_gsum(const PubKeyT& pk, const CipherT& X, uint32_t lid) {
+    FpT zero{};
+    zero.lo = 0;
+    zero.hi = 0;
+    if (lid >= X.L.size()) return zero;
+    return engine_for(pk).template layer_gsums<PubKeyT, CipherT, FpT>(pk, std::vector<const CipherT*>{&X})[0][lid];
+}
+
+// dump_metrics (metrics.hpp:13-41): one CSV row per call appended to pvac_metrics.csv in the working
+// directory, the header line once per process (before the first row, as the reference writes it on
+// every first call of a process), the density from sigma_density above with six fixed decimals.
+namespace detail {
+struct metrics_csv {   // one per process, whatever types dump_metrics is instantiated on
+    std::ofstream f;
+    bool ready = false;
+};
+inline metrics_csv& metrics_csv_file() {
+    static metrics_csv m;
+    return m;
+}
+}  // namespace detail
+
+template <class PubKeyT, class CipherT, class FpT>
+void dump_metrics(const PubKeyT& pk, const char* tag, const CipherT& C, const FpT& val) {
+    detail::metrics_csv& m = detail::metrics_csv_file();
+    if (!m.ready) {
+        m.f.open("pvac_metrics.csv", std::ios::app);
+        if (!m.f) return;
+        m.f << "tag,edges,layers,sigma_density,value_lo,value_hi\n";
+        m.ready = true;
+    }
+    const double density = sigma_density(pk, C);
+    m.f << tag << ',' << C.E.size() << ',' << C.L.size() << ',' << std::fixed << std::setprecision(6) << density << ','
+        << val.lo << ',' << val.hi << "\n";
+    m.f.flush();   // a reader in the same process sees the row (the reference leaves it to the stream's destructor)
 }
 
 // ---- encryption / decryption (ops/encrypt.hpp:289, ops/decrypt.hpp:62) --------------------

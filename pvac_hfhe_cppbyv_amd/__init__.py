@@ -13,6 +13,7 @@ Host-side cipher representation mirrors pvac::Cipher (reference core/types.hpp:9
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass
 
@@ -182,6 +183,9 @@ def load_library(path: str = _LIB_PATH) -> C.CDLL:
         "pvac_hip_batch_digest": ([vp, C.POINTER(CtBatch), vp], i32),
         "pvac_hip_batch_sumdigest": ([vp, C.POINTER(CtBatch), vp], i32),
         "pvac_hip_commit_ct": ([vp, C.POINTER(CtBatch), vp], i32),
+        "pvac_hip_sigma_bytehist": ([vp, C.POINTER(CtBatch), vp], i32),
+        "pvac_hip_layer_gsum": ([vp, C.POINTER(CtBatch), vp, vp], i32),
+        "pvac_hip_metrics_path_count": ([vp, C.POINTER(u64)], i32),
         "pvac_hip_batch_pack": ([vp, C.POINTER(CtBatch), C.POINTER(CtBatch), C.POINTER(u64)], i32),
         "pvac_hip_bucket_count": ([u64], u64),
         "pvac_hip_chain_partition": ([u64, u64, u32, vp], i32),
@@ -1010,6 +1014,58 @@ class Engine:
             sx.sigma = None
         self._check(self.lib.pvac_hip_commit_ct(self.ctx, C.byref(sx), C.c_void_p(out.data_ptr())))
         return out[:X.n].cpu().numpy()
+
+    # ---- metrics (utils/metrics.hpp)
+    def sigma_bytehist(self, X: DeviceBatch):
+        """Byte histogram of every cipher's sigma rows (pvac_hip_sigma_bytehist): an (n, 256) device int64
+        tensor of exact counts, hist[i, b] = bytes equal to b among the ceil(m_bits / 64) words of each row."""
+        out = self.torch.empty((max(X.n, 1), 256), dtype=self.torch.int64, device=self.device)
+        sx = X.struct()
+        self._check(self.lib.pvac_hip_sigma_bytehist(self.ctx, C.byref(sx), C.c_void_p(out.data_ptr())))
+        return out[:X.n]
+
+    @staticmethod
+    def shannon_of_counts(freq):
+        """The reference's entropy expression (utils/metrics.hpp:58-67) on 256 exact counts, in its order."""
+        total = sum(int(f) for f in freq)
+        if total == 0:
+            return 0.0
+        H = 0.0
+        for f in freq:
+            if int(f) > 0:
+                p = float(int(f)) / total
+                H -= p * math.log2(p)
+        return H
+
+    def sigma_shannon(self, X: DeviceBatch):
+        """sigma_shannon (utils/metrics.hpp:43-68) per cipher as numpy float64: the counts from the device,
+        the 256 logarithms per cipher on the host in the reference's order; 0.0 for an empty cipher."""
+        h = self.sigma_bytehist(X).cpu().numpy().view(np.uint64)
+        return np.array([self.shannon_of_counts(row) for row in h], np.float64)
+
+    def layer_gsum(self, X: DeviceBatch, status=False):
+        """agg_layer_gsum (utils/metrics.hpp:70-86) of every layer of every cipher (pvac_hip_layer_gsum;
+        needs set_powg): a (layer slots, 2) device int64 tensor of (lo, hi) words parallel to X.layers;
+        slots outside a cipher's l_cnt keep the 0xFF fill. status=True also returns the per-cipher
+        status as numpy u32."""
+        torch = self.torch
+        out = torch.full((max(X.layers.shape[0] if X.layers is not None else 0, 1), 2), -1, dtype=torch.int64,
+                         device=self.device)
+        st = torch.zeros(max(X.n, 1), dtype=torch.int32, device=self.device)
+        sx = X.struct()
+        self._check(self.lib.pvac_hip_layer_gsum(self.ctx, C.byref(sx), C.c_void_p(out.data_ptr()),
+                                                 C.c_void_p(st.data_ptr())))
+        if status:
+            return out, st[:X.n].cpu().numpy().view(np.uint32)
+        return out
+
+    def metrics_path_counts(self):
+        """Since the context was created: sigma_bytehist calls on the 16-byte / 8-byte load path, and
+        layer_gsum ciphers on the wave / workgroup / large route."""
+        v = (C.c_uint64 * 5)()
+        self._check(self.lib.pvac_hip_metrics_path_count(self.ctx, v))
+        return {"hist_wide": int(v[0]), "hist_strided": int(v[1]), "gsum_wave": int(v[2]), "gsum_workgroup": int(v[3]),
+                "gsum_large": int(v[4])}
 
     def pack(self, X: DeviceBatch) -> DeviceBatch:
         """X's used rows back to back (pvac_hip_batch_pack): dense offsets, arrays of exactly the

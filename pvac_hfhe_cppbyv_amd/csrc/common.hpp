@@ -557,4 +557,22 @@ hipError_t launch_lincomb_layout(const lincomb_args& a, uint64_t total_layers, u
 // exec: layers, edges (and sigma rows) of every one-pass segment, then C.l_cnt / C.e_cnt
 hipError_t launch_lincomb_copy(const lincomb_args& a, uint64_t total_layers, uint64_t total_edges, hipStream_t st);
 
+// ---- metrics (k_metrics.hip, utils/metrics.hpp:43-86)
+// hist[256 i + b] (device u64) = bytes equal to b among the first ceil(m_bits / 64) words of cipher i's
+// sigma rows; every entry is written. *wide_out: 1 = the 16-byte-load path served the call, 0 = the 8-byte one
+hipError_t launch_sigma_bytehist(const pvac_ct_batch& X, uint32_t m_bits, int num_cus, unsigned long long* hist, int* wide_out,
+                                 hipStream_t st);
+// layer_gsum's size pass: out (8 device u64, zeroed by the caller) = most layers of a cipher whose table
+// lives in dynamic LDS, most layers of a cipher that needs a global slab, ciphers on the wave / workgroup /
+// large route, ciphers that need a slab, ciphers beyond 2^28 layers (refused by the host)
+constexpr int kGsumSizeWords = 8;
+hipError_t launch_gsum_sizes(const pvac_ct_batch& X, unsigned long long* out, hipStream_t st);
+// global scratch the launch needs for these sizes (0: every table fits LDS)
+uint64_t gsum_slab_bytes(uint64_t n, const unsigned long long* sizes_host, int num_cus);
+// gsum[2 (l_off[i] + l)], [.. + 1] = agg_layer_gsum(X_i, l) for l < l_cnt[i]; status nullable;
+// ticket: one device u64 (the slab counter, zeroed by the launch)
+hipError_t launch_layer_gsum(const pvac_ct_batch& X, const uint64_t* powg, uint32_t Bm, const unsigned long long* sizes_host,
+                             uint64_t* gsum, uint32_t* status, uint8_t* slabs, unsigned long long* ticket, int num_cus,
+                             hipStream_t st);
+
 }  // namespace pvhip

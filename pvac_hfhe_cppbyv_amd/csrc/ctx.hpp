@@ -221,6 +221,11 @@ struct pvac_hip_ctx {
         pvhip::dev_buf<uint8_t> scratch;         // layer tables beyond LDS (global slabs)
         uint64_t path[2] = {};                   // calls with the tables in LDS / in global slabs
     } check;
+    struct {   // sigma_bytehist / layer_gsum (rt_metrics.cpp, k_metrics.hip)
+        pvhip::dev_buf<unsigned long long> sizes;   // layer_gsum's size pass, then the slab ticket
+        pvhip::dev_buf<uint8_t> slabs;              // layer tables beyond LDS
+        uint64_t path[5] = {};                      // bytehist calls wide / strided; gsum ciphers wave / workgroup / large
+    } metrics;
     struct {
         bool on = false;
         std::map<std::string, pvhip::timer_rec> timers;
