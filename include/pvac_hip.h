@@ -692,6 +692,69 @@ int pvac_ct_serialized_size(const pvac_ct_batch* X, uint32_t sigma_bits, uint64_
 int pvac_ct_write(const pvac_ct_batch* X, uint32_t sigma_bits, uint8_t* out, size_t capacity, uint64_t* written,
                   int threads);
 
+/* ---------------------------------------------------------------- .ct codec (device memory)
+ * The same format where the ciphers are: a resident batch becomes a byte-exact .ct file image in device
+ * memory (one copy to pinned memory and one write() finish a save), and an uploaded image becomes a
+ * resident batch. The host codec above is the specification: the image is exactly pvac_ct_write's
+ * bytes, the parsed arrays exactly pvac_ct_parse's. File I/O stays with the caller.
+ *
+ * pvac_ct_index (host, no context): pvac_ct_scan plus the byte offset of every cipher's |L| field:
+ * pos (HOST, n_ciphers + 1 words), pos[0] = 16, pos[n] = len. Same validation and codes as pvac_ct_scan;
+ * PVAC_ENOMEM (with *info filled) when pos_cap < n_ciphers + 1. A file whose edges disagree on nbits is
+ * flagged (PVAC_CT_MIXED_SIGMA) here and refused by the device parser, as by the host parser.
+ *
+ * Image buffer: `image` (DEVICE) is 16-byte aligned (PVAC_EINVAL otherwise) and its allocation holds
+ * (cap + 15) & ~15 bytes for a write, (len + 15) & ~15 bytes for a parse: the kernels move aligned
+ * 16-byte granules. The writer changes no byte at or after pos[n]; the parser reads no byte at or after
+ * the rounded length.
+ *
+ * pvac_hip_ct_image_plan: the sizes of X's image. nbits = X->sigma ? sigma_bits : 0
+ * (pvac_ct_serialized_size's rule). pos (DEVICE, X->n + 1 words) as above, *bytes (HOST) = pos[n].
+ * Dense or capacity-padded CSR (a ct_mul_exec output); slots past the counts are never read.
+ * PVAC_EINVAL when X->sigma is set and ceil(sigma_bits / 64) > X->sigma_words, and (with *bytes set) for a
+ * layer whose rule >= 256: the host writer sizes such a layer by the u32 and writes its low byte, so
+ * its output is not a file. PVAC_ENOSYS for sigma_bits above 130816 (an edge record beyond a 16 KiB
+ * tile), sigma_words above 4096 or 2^31 - 1 ciphers or more. Synchronises once.
+ *
+ * pvac_hip_ct_image_write: image[0, pos[n]) = exactly the bytes pvac_ct_write produces for X's used rows:
+ * a rule other than 0 or 1 writes its byte and 24 zero bytes, PROD writes pa, pb only, n = 0 gives the
+ * 16-byte header, sigma words are copied whole (nw = ceil(nbits / 64) words per row with row stride
+ * sigma_words, bits past nbits included). It takes this context's latest image plan only: the pos that
+ * plan filled, for the same X and sigma_bits (PVAC_EINVAL otherwise). PVAC_ERANGE when pos[n] > cap
+ * (pvac_ct_write's code). Enqueued on the context's stream; not synchronous. Timing label "ct_image_write".
+ *
+ * pvac_hip_ct_image_parse: image (DEVICE, the len bytes of a .ct file) with pos (DEVICE, n + 1 words: the
+ * caller uploads pvac_ct_index's) -> X as dense CSR, exactly the arrays pvac_ct_parse produces: l_off /
+ * e_off are exclusive scans of the counts read from the image, X->n is set; layer records are written in
+ * full (40 bytes: PROD has ztag = nonce = 0, an unknown rule is kept with everything else 0, pad = 0);
+ * sigma words from nw up to X->sigma_words are zeroed; X->sigma == NULL skips sigma. X's index arrays
+ * hold n entries, X->layers layer_cap slots, the edge arrays (and X->sigma) edge_cap slots. Every edge
+ * of the image carries nbits = sigma_bits (pvac_ct_file_info.sigma_bits).
+ * Validation comes before any row is written, from pos, len and the two count words of each cipher alone:
+ * pos non-decreasing, pos[0] == 16, pos[n] == len, 8 + |E| eb <= pos[i + 1] - pos[i] with
+ * eb = 28 + 8 nw, and the walk of |L| layer records from pos[i] + 8 ending exactly at
+ * pos[i + 1] - |E| eb. status (DEVICE, n u32, nullable): 0 ok, 1 the cipher fails one of these. Any
+ * status 1 returns PVAC_EINVAL, totals above layer_cap or edge_cap PVAC_ENOMEM, both with nothing
+ * written to X. An edge whose nbits field differs from sigma_bits gives its cipher status 2 and the call
+ * PVAC_EINVAL; X's rows are unspecified then (every write stays in bounds). The 16 header bytes are not
+ * checked beyond pos[0]: pvac_ct_index did. PVAC_ENOSYS as for the plan. Synchronises once, at its end:
+ * the row kernels take the validation's verdict on the device. Timing label "ct_image_parse".
+ *
+ * Work is dealt in tiles of whole edge records (at most 16 KiB of image) numbered through the batch, so
+ * one cipher of 345 K edges and 2^20 small ones both fill the device. Sigma rows move 16 bytes at a
+ * time when nw and sigma_words are even and X->sigma is 16-byte aligned, 8 bytes at a time otherwise.
+ * pvac_hip_ct_image_path_count, since the context was created: out[0] / out[1] = writes served by the
+ * 16-byte / the 8-byte sigma path, out[2] / out[3] the same for parses; a weights-only call (no sigma,
+ * or sigma_bits = 0 on a write) counts under the 8-byte path. */
+int pvac_ct_index(const uint8_t* buf, size_t len, pvac_ct_file_info* info, uint64_t* pos, size_t pos_cap);
+int pvac_hip_ct_image_plan(pvac_hip_ctx* ctx, const pvac_ct_batch* X, uint32_t sigma_bits, uint64_t* pos, uint64_t* bytes);
+int pvac_hip_ct_image_write(pvac_hip_ctx* ctx, const pvac_ct_batch* X, uint32_t sigma_bits, const uint64_t* pos,
+                            uint8_t* image, uint64_t cap);
+int pvac_hip_ct_image_parse(pvac_hip_ctx* ctx, const uint8_t* image, uint64_t len, const uint64_t* pos, uint64_t n,
+                            uint32_t sigma_bits, pvac_ct_batch* X, uint64_t layer_cap, uint64_t edge_cap,
+                            uint32_t* status);
+int pvac_hip_ct_image_path_count(pvac_hip_ctx* ctx, uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -435,6 +435,13 @@ lincomb_lists flatten_lincomb(size_t n_x, const std::vector<uint64_t>& seg_off, 
 }  // namespace detail
 
 // One device context per (device, canon_tag); owns the device copy of pk.H for sigma.
+// A batch resident on the device that owns its arrays (Engine::batch_from_image).
+struct device_batch {
+    detail::batch arrays;
+    uint32_t sigma_bits = 0;   // nbits of every edge's sigma in the file it came from (0: no sigma rows)
+    pvac_ct_batch view() { return arrays.view(sigma_bits != 0); }
+};
+
 class Engine {
 public:
     Engine(int device, const pvac_hip_params& prm) : prm_(prm) {
@@ -1293,6 +1300,53 @@ public:
                 out[i][l].hi = w[2 * (x.l_off[i] + l) + 1];
             }
         }
+        return out;
+    }
+
+    // ---- the device .ct codec (pvac_hip_ct_image_plan / _write / _parse)
+    // The .ct file image of a resident batch (a device view, dense or capacity-padded CSR): built on
+    // the device and copied to the host once; exactly the bytes pvac_ct_write gives for its used rows.
+    // A view without sigma is written weights-only.
+    std::vector<uint8_t> ct_image(const pvac_ct_batch& dev_view, uint32_t sigma_bits) {
+        detail::dev_array<uint64_t> pos(dev_view.n + 1);
+        uint64_t bytes = 0;
+        check(pvac_hip_ct_image_plan(ctx_, &dev_view, sigma_bits, pos.p, &bytes));
+        detail::dev_array<uint8_t> image((bytes + 15) & ~15ull);
+        check(pvac_hip_ct_image_write(ctx_, &dev_view, sigma_bits, pos.p, image.p, bytes));
+        std::vector<uint8_t> out(bytes);
+        image.download(out.data(), bytes, stream_);
+        detail::hip_ok(hipStreamSynchronize(stream_), "sync");
+        return out;
+    }
+
+    // A .ct file's bytes as a resident batch that owns its arrays: the ciphers are indexed on the
+    // host (offsets only), the bytes uploaded once and parsed on the device into exactly the arrays
+    // pvac_ct_parse gives. Sigma rows are kept when the file carries them.
+    device_batch batch_from_image(const std::vector<uint8_t>& file) {
+        pvac_ct_file_info info{};
+        std::vector<uint64_t> pos(64);
+        int rc = pvac_ct_index(file.data(), file.size(), &info, pos.data(), pos.size());
+        if (rc == PVAC_ENOMEM) {
+            pos.resize(info.n_ciphers + 1);
+            rc = pvac_ct_index(file.data(), file.size(), &info, pos.data(), pos.size());
+        }
+        if (rc) throw Error(rc, "batch_from_image: not a .ct file image");
+        if (info.flags & PVAC_CT_MIXED_SIGMA) throw Error(PVAC_ENOSYS, "batch_from_image: the edges disagree on sigma nbits");
+        const size_t n = info.n_ciphers;
+        const bool sig = info.sigma_words != 0;
+        detail::dev_array<uint8_t> image((file.size() + 15) & ~size_t(15));
+        image.upload(file.data(), file.size(), stream_);
+        detail::dev_array<uint64_t> dpos(n + 1);
+        dpos.upload(pos.data(), n + 1, stream_);
+        device_batch out;
+        out.sigma_bits = info.sigma_bits;
+        detail::batch& b = out.arrays;
+        b.d_l_off.alloc(n); b.d_l_cnt.alloc(n); b.d_e_off.alloc(n); b.d_e_cnt.alloc(n);
+        detail::alloc_out(b, n, info.total_layers, info.total_edges, info.sigma_words, sig);
+        pvac_ct_batch v = b.view(sig);
+        v.n = n;
+        check(pvac_hip_ct_image_parse(ctx_, image.p, file.size(), dpos.p, n, info.sigma_bits, &v, info.total_layers,
+                                      info.total_edges, nullptr));
         return out;
     }
 

@@ -208,6 +208,11 @@ def load_library(path: str = _LIB_PATH) -> C.CDLL:
         "pvac_ct_parse": ([vp, C.c_size_t, C.POINTER(CtBatch), i32], i32),
         "pvac_ct_serialized_size": ([C.POINTER(CtBatch), u32, C.POINTER(u64)], i32),
         "pvac_ct_write": ([C.POINTER(CtBatch), u32, vp, C.c_size_t, C.POINTER(u64), i32], i32),
+        "pvac_ct_index": ([vp, C.c_size_t, vp, vp, C.c_size_t], i32),
+        "pvac_hip_ct_image_plan": ([vp, C.POINTER(CtBatch), u32, vp, C.POINTER(u64)], i32),
+        "pvac_hip_ct_image_write": ([vp, C.POINTER(CtBatch), u32, vp, vp, u64], i32),
+        "pvac_hip_ct_image_parse": ([vp, vp, u64, vp, u64, u32, C.POINTER(CtBatch), u64, u64, vp], i32),
+        "pvac_hip_ct_image_path_count": ([vp, C.POINTER(u64)], i32),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)
@@ -1082,6 +1087,54 @@ class Engine:
         nl, ne = int(tot[0]), int(tot[1])
         return DeviceBatch(X.n, D.l_off, D.l_cnt, D.layers[:nl], D.e_off, D.e_cnt, D.meta[:ne], D.w_lo[:ne],
                            D.w_hi[:ne], D.sigma[:ne] if sig else None)
+
+    # ---- the device .ct codec
+    def ct_image(self, batch: DeviceBatch, sigma_bits=8192, return_pos=False):
+        """The .ct file image of `batch` (dense or capacity-padded) as a device uint8 tensor: exactly the
+        bytes codec.write_ct gives for its used rows (pvac_hip_ct_image_plan / _write). A batch without
+        sigma is written weights-only (nbits = 0). return_pos=True also returns the device int64 tensor of
+        the n + 1 cipher offsets (what ct_from_image takes)."""
+        torch = self.torch
+        pos = torch.empty(batch.n + 1, dtype=torch.int64, device=self.device)
+        size = C.c_uint64()
+        sx = batch.struct()
+        self._check(self.lib.pvac_hip_ct_image_plan(self.ctx, C.byref(sx), sigma_bits, C.c_void_p(pos.data_ptr()),
+                                                    C.byref(size)))
+        nbytes = int(size.value)
+        buf = torch.empty((nbytes + 15) & ~15, dtype=torch.uint8, device=self.device)
+        self._check(self.lib.pvac_hip_ct_image_write(self.ctx, C.byref(sx), sigma_bits, C.c_void_p(pos.data_ptr()),
+                                                     C.c_void_p(buf.data_ptr()), nbytes))
+        return (buf[:nbytes], pos) if return_pos else buf[:nbytes]
+
+    def ct_from_image(self, image, pos, n, sigma_bits, layer_cap, edge_cap, sigma=True, status=False, out=None,
+                      sigma_words=128):
+        """A device .ct image (uint8 tensor, 16-byte aligned, its allocation rounded up to 16 bytes) with
+        the cipher offsets `pos` (device int64, n + 1: codec.index's) as a dense DeviceBatch: exactly the
+        arrays codec.read_ct_soa gives (pvac_hip_ct_image_parse). sigma=True keeps the sigma rows
+        (sigma_words words per edge); out= gives the DeviceBatch to fill instead (its arrays sized by the caps).
+        status=True returns (code, batch, per-cipher status as numpy u32) instead of raising."""
+        torch = self.torch
+        X = out
+        if X is None:
+            X = DeviceBatch.empty(n, layer_cap, edge_cap, self.device)
+            if sigma:
+                X.sigma = torch.empty((max(int(edge_cap), 1), sigma_words), dtype=torch.int64, device=self.device)
+        X.n = n
+        st = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        sx = X.struct()
+        rc = self.lib.pvac_hip_ct_image_parse(self.ctx, C.c_void_p(image.data_ptr()), image.numel(),
+                                              C.c_void_p(pos.data_ptr()), n, sigma_bits, C.byref(sx), int(layer_cap),
+                                              int(edge_cap), C.c_void_p(st.data_ptr()))
+        if status:
+            return rc, X, st[:n].cpu().numpy().view(np.uint32)
+        self._check(rc)
+        return X
+
+    def ct_image_path_counts(self):
+        """Since the context was created: image writes on the 16-byte / 8-byte sigma path, then parses."""
+        v = (C.c_uint64 * 4)()
+        self._check(self.lib.pvac_hip_ct_image_path_count(self.ctx, v))
+        return {"write_wide": int(v[0]), "write_narrow": int(v[1]), "parse_wide": int(v[2]), "parse_narrow": int(v[3])}
 
     # ---- timing
     def timing(self, on=True):

@@ -6,6 +6,9 @@ native codec (csrc/ct_codec.cpp, C ABI pvac_ct_scan / pvac_ct_parse / pvac_ct_wr
   write_ct(ciphers)       -> bytes                       (list[HostCipher] or an SoA dict)
   load_ct(src, device)    -> DeviceBatch                 (parse on the host, one H2D copy per array)
   save_ct(batch, path)                                   (DeviceBatch -> file)
+  index(src)              -> (CtFileInfo, pos)           (pvac_ct_index: every cipher's byte offset)
+  save_ct_device(engine, batch, path)                    (image built on the device, one copy, one write)
+  load_ct_device(engine, src) -> DeviceBatch             (host index, one upload, parsed on the device)
 
 PROD layers carry no seed on disk (the reference's putLayer writes pa/pb only), so parsed PROD
 layers have ztag = nonce = 0; sigmas round-trip bit-exactly.
@@ -145,3 +148,55 @@ def save_ct(batch: DeviceBatch, path, sigma_bits: int = 8192, threads: int = 0) 
     with open(path, "wb") as f:
         f.write(data)
     return len(data)
+
+
+def index(src):
+    """pvac_ct_index: (CtFileInfo, pos) with pos the n + 1 byte offsets of the ciphers (pos[0] = 16,
+    pos[n] = the file's length) as numpy u64."""
+    buf = _bytes(src)
+    lib = _lib()
+    info = CtFileInfo()
+    pos = np.zeros(4096, np.uint64)
+    rc = lib.pvac_ct_index(_ptr(buf), buf.size, C.byref(info), _ptr(pos), pos.size)
+    if rc == -12:   # PVAC_ENOMEM: info holds the cipher count
+        pos = np.zeros(int(info.n_ciphers) + 1, np.uint64)
+        rc = lib.pvac_ct_index(_ptr(buf), buf.size, C.byref(info), _ptr(pos), pos.size)
+    _check(rc, "pvac_ct_index")
+    return info, pos[: int(info.n_ciphers) + 1].copy()
+
+
+def save_ct_device(engine, batch: DeviceBatch, path, sigma_bits: int = 8192) -> int:
+    """The file image is built on the device (Engine.ct_image: plan and write), copied once into pinned
+    host memory and written out."""
+    import torch
+    img = engine.ct_image(batch, sigma_bits)
+    host = torch.empty(img.numel(), dtype=torch.uint8, pin_memory=True)
+    host.copy_(img)
+    with open(path, "wb") as f:
+        f.write(host.numpy().data)
+    return img.numel()
+
+
+def load_ct_device(engine, src, sigma: bool = True) -> DeviceBatch:
+    """Index on the host (cipher offsets only), upload the raw bytes and the offsets once, parse on the
+    device (Engine.ct_from_image). The bytes are read straight into pinned memory."""
+    import torch
+    if isinstance(src, (str, os.PathLike)):
+        size = os.path.getsize(src)
+        host = torch.empty((size + 15) & ~15, dtype=torch.uint8, pin_memory=True)
+        with open(src, "rb") as f:
+            if f.readinto(host.numpy()[:size]) != size:
+                raise PvacError(f"load_ct_device: short read of {src}")
+    else:
+        buf = _bytes(src)
+        size = buf.size
+        host = torch.empty((size + 15) & ~15, dtype=torch.uint8, pin_memory=True)
+        host.numpy()[:size] = buf
+    info, pos = index(host.numpy()[:size])
+    if info.flags & CT_MIXED_SIGMA:
+        raise PvacError("load_ct_device: the edges disagree on sigma nbits")
+    image = host.to(engine.device)[:size]
+    dpos = torch.from_numpy(pos.view(np.int64)).to(engine.device)
+    return engine.ct_from_image(image, dpos, int(info.n_ciphers), int(info.sigma_bits), int(info.total_layers),
+                                int(info.total_edges), sigma=sigma and info.sigma_words > 0,
+                                sigma_words=max(int(info.sigma_words), 1))

@@ -575,4 +575,23 @@ hipError_t launch_layer_gsum(const pvac_ct_batch& X, const uint64_t* powg, uint3
                              uint64_t* gsum, uint32_t* status, uint8_t* slabs, unsigned long long* ticket, int num_cus,
                              hipStream_t st);
 
+// ---- device .ct codec (k_ct_image.hip, ct_image.hpp): a resident batch <-> a .ct file image in device memory
+// ctl: device words the passes report in and the parse's row kernels read their go-ahead from.
+//   plan : 0 = sum of the cipher sizes (image bytes - 16), 1 = edge tiles, 2 = layers with a rule >= 256,
+//          3 = edges of the largest tile
+//   parse: 0 / 1 = layer and edge totals, 2 = edge tiles, 3 = malformed ciphers, 4 = edges whose nbits differs
+constexpr int kCtImageCtlWords = 8;
+// sizes of X's image: pos (n + 1), and toff (n; the exclusive scan of the per-cipher edge tile counts);
+// sz: n words of scratch. Nothing is read back here.
+hipError_t launch_ct_image_plan(const pvac_ct_batch& X, uint32_t nbits, uint64_t* sz, uint64_t* toff, uint64_t* scan_scratch,
+                                unsigned long long* ctl, uint64_t* pos, hipStream_t st);
+// image[0, pos[n]) from X with the plan's pos / toff / tile count / largest tile; wide: sigma rows by 16-byte loads
+hipError_t launch_ct_image_write(const pvac_ct_batch& X, uint32_t nbits, const uint64_t* pos, const uint64_t* toff,
+                                 uint64_t ntiles, uint32_t max_tile_edges, bool wide, int num_cus, uint8_t* image, hipStream_t st);
+// validation, scans and the row kernels (which write X only when ctl says every cipher is well-formed
+// and the totals fit the caps); words: 5 (n + 1) words of scratch; wide: sigma rows by 16-byte stores
+hipError_t launch_ct_image_parse(const uint8_t* image, uint64_t len, const uint64_t* pos, uint64_t n, uint32_t nbits,
+                                 const pvac_ct_batch& X, uint64_t layer_cap, uint64_t edge_cap, uint32_t* status, uint64_t* words,
+                                 uint64_t* scan_scratch, unsigned long long* ctl, bool wide, int num_cus, hipStream_t st);
+
 }  // namespace pvhip

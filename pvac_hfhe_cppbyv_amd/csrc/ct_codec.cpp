@@ -139,6 +139,28 @@ int pvac_ct_scan(const uint8_t* buf, size_t len, pvac_ct_file_info* info) {
     return PVAC_OK;
 }
 
+int pvac_ct_index(const uint8_t* buf, size_t len, pvac_ct_file_info* info, uint64_t* pos, size_t pos_cap) {
+    if (!buf || !info || !pos) return PVAC_EINVAL;
+    std::vector<cipher_span> spans;
+    uint32_t nbits = 0;
+    bool mixed = false;
+    const int rc = walk(buf, len, spans, nbits, mixed);
+    if (rc) return rc;
+    std::memset(info, 0, sizeof *info);
+    info->n_ciphers = spans.size();
+    for (const auto& s : spans) {
+        info->total_layers += s.nL;
+        info->total_edges += s.nE;
+    }
+    info->sigma_bits = nbits;
+    info->sigma_words = (nbits + 63u) / 64u;
+    info->flags = mixed ? PVAC_CT_MIXED_SIGMA : 0u;
+    if (pos_cap < spans.size() + 1) return PVAC_ENOMEM;
+    for (size_t c = 0; c < spans.size(); ++c) pos[c] = spans[c].off;
+    pos[spans.size()] = len;
+    return PVAC_OK;
+}
+
 int pvac_ct_parse(const uint8_t* buf, size_t len, pvac_ct_batch* X, int threads) {
     if (!buf || !X) return PVAC_EINVAL;
     std::vector<cipher_span> spans;

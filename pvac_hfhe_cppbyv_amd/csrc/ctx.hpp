@@ -226,6 +226,15 @@ struct pvac_hip_ctx {
         pvhip::dev_buf<uint8_t> slabs;              // layer tables beyond LDS
         uint64_t path[5] = {};                      // bytehist calls wide / strided; gsum ciphers wave / workgroup / large
     } metrics;
+    struct {   // the device .ct codec (rt_codec.cpp, k_ct_image.hip)
+        pvhip::dev_buf<uint64_t> sz, toff;          // the latest image plan: size scratch, edge tile offsets
+        pvhip::dev_buf<uint64_t> words;             // a parse's counts, offsets and tile offsets
+        pvhip::dev_buf<unsigned long long> ctl;     // kCtImageCtlWords
+        const uint64_t* plan_pos = nullptr;         // the latest image plan (null: none): its pos array,
+        uint64_t plan_n = 0, plan_bytes = 0, plan_tiles = 0;   // ... shape and totals
+        uint32_t plan_nbits = 0, plan_tile_edges = 0;
+        uint64_t path[4] = {};                      // writes wide / 8-byte sigma path, parses wide / 8-byte
+    } codec;
     struct {
         bool on = false;
         std::map<std::string, pvhip::timer_rec> timers;
