@@ -153,7 +153,8 @@ int pvac_hip_alu_ceiling(pvac_hip_ctx* ctx, int kind, double* per_s);
 int pvac_hip_issue_probe(pvac_hip_ctx* ctx, int op, int waves_per_simd, double* per_s, double* clock_hz);
 /* Per-kernel device timing (HIP events on the ctx stream) for the roofline report. */
 int pvac_hip_timing_enable(pvac_hip_ctx* ctx, int on);
-/* kernel_name: "fp_binop", "ct_mul_small", "ct_mul_large", "ct_add", "sigma", ... ; returns
+/* kernel_name: "fp_binop", "ct_mul_small", "ct_mul_large", "ct_add", "sigma", ... (the deep kernels:
+ * "large_lists_deep", "large_layers_deep", both inside "ct_mul_large", and "ct_add_deep"); returns
  * accumulated milliseconds and launch count since the last reset (synchronises). */
 int pvac_hip_timing_get(pvac_hip_ctx* ctx, const char* kernel_name, double* ms, uint64_t* launches);
 int pvac_hip_timing_reset(pvac_hip_ctx* ctx);
@@ -203,6 +204,25 @@ int pvac_hip_ct_mul_redo_count(pvac_hip_ctx* ctx, uint64_t* out);
  * LDS-resident fresh-shape kernel, out[1] the general path (redo launches included), out[2] of
  * those the per-A-edge emit order, out[3] the direct mode (positions from key presence). */
 int pvac_hip_ct_mul_path_count(pvac_hip_ctx* ctx, uint64_t* out);
+/* The layer limit of a context. A ct_mul pair is accepted while its layers before compaction,
+ * |A.L| + |B.L| + |A.L||B.L|, are at most the limit (PVAC_ENOSYS above it; the bounds |A.L||B.L|B < 2^31
+ * and |A.E||B.E| < 2^32 hold at any limit), and ct_add / ct_sub while the largest |A.L| + |B.L| of the
+ * batch is at most max(30000, limit). Up to PVAC_LAYER_LIMIT_DEFAULT layers (ct_add: 30000) the per-layer
+ * tables of a pair live in LDS; a pair above runs the deep kernels (k_large_deep.hip), which keep them in
+ * the pair's global scratch and change no result. The default is kept on purpose: the general path's
+ * scratch is about 16 words per key slot (|A.L||B.L|B slots), at most ~350 MB at the default limit and
+ * over 100 GB near 2^31 slots, so a caller raises the limit knowing what its ciphers cost.
+ * set: PVAC_EINVAL outside [PVAC_LAYER_LIMIT_DEFAULT, PVAC_LAYER_LIMIT_MAX]. The workers of
+ * pvac_hip_ct_mul_chain take the calling context's limit at each call. ct_lincomb, compact and ct_recrypt
+ * keep their 30000-layer refusals at any limit; an over-budget ct_add pair (guard_budget) of any depth
+ * takes the merge kernel, whose layer table is in global scratch already. */
+#define PVAC_LAYER_LIMIT_DEFAULT 16384u
+#define PVAC_LAYER_LIMIT_MAX (1u << 24)
+int pvac_hip_ctx_set_layer_limit(pvac_hip_ctx* ctx, uint32_t max_layers); /* DEFAULT..MAX, else PVAC_EINVAL */
+int pvac_hip_ctx_layer_limit(pvac_hip_ctx* ctx, uint32_t* out);
+/* Since the context was created: out[0] = ct_mul pairs run by the deep kernels (a chain's workers
+ * included), out[1] = ct_add / ct_sub calls run by the deep kernel. */
+int pvac_hip_deep_path_count(pvac_hip_ctx* ctx, uint64_t out[2]);
 /* Per-pair outcome of the last ct_mul_exec, copied (stream-ordered) to the DEVICE array out[n]:
  * 0 = reference hash order, 1 = canonical (layer, idx, P<M) order (guard_budget or
  * PVAC_MUL_ORDER_CANONICAL), 2 = rejected. Rejection is stricter than the reference: an edge with
@@ -363,7 +383,9 @@ int pvac_hip_chain_partition(uint64_t n_inputs, uint64_t chunk, uint32_t parts, 
 /* ct_add / ct_sub (ops/arithmetic.hpp:12-31, 43-45; combine_ciphers ops/encrypt.hpp:260-279).
  * negate_b != 0 gives ct_sub (B's weights scaled by p-1). Dense CSR output: the plan writes
  * C->l_off/e_off as exclusive scans of |A.L|+|B.L| and |A.E|+|B.E|. Sigmas are carried when
- * A, B and C all have sigma != NULL. */
+ * A, B and C all have sigma != NULL. exec: PVAC_ENOSYS when a pair has more than max(30000, the
+ * context's layer limit) layers (pvac_hip_ctx_set_layer_limit); a call whose largest pair has more
+ * than 30000 runs k_ct_add_deep (timing name "ct_add_deep"), its keep / remap table in global scratch. */
 int pvac_hip_ct_add_plan(pvac_hip_ctx* ctx, const pvac_ct_batch* A, const pvac_ct_batch* B, pvac_ct_batch* C,
                          pvac_hip_plan* plan);
 int pvac_hip_ct_add_exec(pvac_hip_ctx* ctx, const pvac_hip_plan* plan, const pvac_ct_batch* A, const pvac_ct_batch* B,

@@ -471,6 +471,17 @@ public:
     pvac_hip_ctx* ctx() const { return ctx_; }
     uint32_t sigma_words() const { return (prm_.m_bits + 63) / 64; }
 
+    // The layers a ct_mul pair may have before compaction, and (with 30000) a ct_add pair in all
+    // (pvac_hip_ctx_set_layer_limit: PVAC_LAYER_LIMIT_DEFAULT .. PVAC_LAYER_LIMIT_MAX; a deep pair's
+    // scratch is about 16 words per key slot). The thread-local engines of the free functions keep
+    // the default.
+    void set_layer_limit(uint32_t max_layers) { check(pvac_hip_ctx_set_layer_limit(ctx_, max_layers)); }
+    uint32_t layer_limit() const {
+        uint32_t v = 0;
+        if (const int rc = pvac_hip_ctx_layer_limit(ctx_, &v)) throw Error(rc, "pvac_hip_ctx_layer_limit");
+        return v;
+    }
+
     // Wall-clock split of the last batched ct_mul, in seconds: host AoS -> SoA, H2D, plan + nonce
     // draws, exec (+ salts, sigma and the device-side pack of the used rows), D2H, SoA -> AoS.
     struct Phases { double to_soa = 0, h2d = 0, plan = 0, exec = 0, d2h = 0, to_aos = 0; };

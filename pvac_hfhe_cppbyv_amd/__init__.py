@@ -31,6 +31,7 @@ CHAIN_CHECK_GSUM = 0x100
 CHAIN_STAGE_INPUTS = 0x200
 CHAIN_IMG_BATCH2 = 0x400
 CHAIN_MAX_DEPTH = 32
+LAYER_LIMIT_DEFAULT, LAYER_LIMIT_MAX = 16384, 1 << 24
 ENC_WITH_SIGMA = 0x1
 ENC_ITEM_FP, ENC_ITEM_VALUE = 0, 1
 TEXT_LEN_HI, TEXT_LEN_CLIPPED = 0x1, 0x2
@@ -147,6 +148,9 @@ def load_library(path: str = _LIB_PATH) -> C.CDLL:
         "pvac_hip_ct_mul_redo_count": ([vp, C.POINTER(u64)], i32),
         "pvac_hip_ct_mul_path_count": ([vp, C.POINTER(u64)], i32),
         "pvac_hip_ctx_set_noise": ([vp, C.c_double, C.c_double, C.c_double], i32),
+        "pvac_hip_ctx_set_layer_limit": ([vp, u32], i32),
+        "pvac_hip_ctx_layer_limit": ([vp, C.POINTER(u32)], i32),
+        "pvac_hip_deep_path_count": ([vp, C.POINTER(u64)], i32),
         "pvac_hip_ct_mul_status": ([vp, vp, C.c_size_t], i32),
         "pvac_hip_ct_mul_chain": ([vp, C.POINTER(CtBatch), C.POINTER(ChainOpts), C.POINTER(ChainStats)], i32),
         "pvac_hip_alu_ceiling": ([vp, i32, C.POINTER(C.c_double)], i32),
@@ -341,7 +345,7 @@ class Engine:
     """One pvac_hip_ctx on one GPU, bound to torch's current stream on that device."""
 
     def __init__(self, device=0, B=337, m_bits=8192, n_bits=16384, h_col_wt=192, x_col_wt=128, err_wt=128,
-                 edge_budget=1200000, canon_tag=0, lib: C.CDLL | None = None):
+                 edge_budget=1200000, canon_tag=0, lib: C.CDLL | None = None, layer_limit=None):
         import torch
         self.torch = torch
         self.lib = lib or load_library()
@@ -354,6 +358,8 @@ class Engine:
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
         self._check(self.lib.pvac_hip_ctx_set_stream(self.ctx, C.c_void_p(stream.cuda_stream)))
+        if layer_limit is not None:
+            self.set_layer_limit(layer_limit)
 
     def __del__(self):
         try:
@@ -692,6 +698,25 @@ class Engine:
         v = (C.c_uint64 * 4)()
         self._check(self.lib.pvac_hip_ct_mul_path_count(self.ctx, v))
         return dict(zip(("fresh", "general", "iblk", "direct"), (int(x) for x in v)))
+
+    def set_layer_limit(self, n):
+        """Layers a ct_mul pair may have before compaction (|A.L| + |B.L| + |A.L||B.L|), LAYER_LIMIT_DEFAULT ..
+        LAYER_LIMIT_MAX; ct_add / ct_sub then take max(30000, n) layers a pair. A pair above the default runs
+        the deep kernels; its scratch is about 16 words per key slot (|A.L||B.L|B slots)."""
+        self._check(self.lib.pvac_hip_ctx_set_layer_limit(self.ctx, int(n)))
+
+    @property
+    def layer_limit(self):
+        v = C.c_uint32(0)
+        self._check(self.lib.pvac_hip_ctx_layer_limit(self.ctx, C.byref(v)))
+        return v.value
+
+    def deep_path_counts(self):
+        """Since the context was created: (ct_mul pairs run by the deep kernels, a chain's workers included;
+        ct_add / ct_sub calls run by the deep kernel)."""
+        v = (C.c_uint64 * 2)()
+        self._check(self.lib.pvac_hip_deep_path_count(self.ctx, v))
+        return int(v[0]), int(v[1])
 
     def ct_mul_status(self, n):
         """Per-pair outcome of the last ct_mul (0 hash order, 1 canonical order, 2 rejected)."""

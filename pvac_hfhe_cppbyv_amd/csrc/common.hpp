@@ -331,7 +331,8 @@ hipError_t launch_commit_ct(const pvac_ct_batch& X, const uint32_t head[14], uin
 // ---- ct_mul, general path (k_mul_large.hip and the k_large_* files): multi-kernel, global scratch, one workgroup
 // per (A-layer, B-layer) product task. The host prepares one descriptor per large pair with
 // ABSOLUTE u32-word offsets into one scratch arena (64-bit arrays on even offsets).
-constexpr uint32_t kLargeLayersMax = 16384;   // |A.L| + |B.L| + |A.L||B.L| handled in LDS
+constexpr uint32_t kLargeLayersMax = 16384;   // |A.L| + |B.L| + |A.L||B.L| handled in LDS; a pair above is a DEEP pair
+static_assert(kLargeLayersMax == PVAC_LAYER_LIMIT_DEFAULT, "the default layer limit is the LDS tables' size");
 constexpr uint32_t kLargeDenseMin = 48;       // dense-owner product mode from this many edges
 
 struct large_desc {
@@ -427,7 +428,8 @@ struct mul_large_args {
                                  // 0 = every other pair (after the products)
     uint32_t all_direct;         // every pair is direct: the per-key kernels are not launched
     uint32_t dir_lb;             // k_large_products_direct: B layers its LDS holds (max |B.L| of the direct pairs)
-    uint32_t pad4;
+    uint32_t deep;               // a deep sub-batch: every pair has Lc > kLargeLayersMax (k_large_deep.hip); max_nA is then
+                                 // the largest |A.E| or |B.E| of its pairs (the lists kernels' edge grids)
     uint64_t* redo_ids;          // pairs the host re-runs on the full layout (shared with the fresh kernel)
     unsigned int* redo_cnt;
     // chain steps (pvac_hip_ct_mul_chain): a pair whose A_img flag is set holds A as a dense image
@@ -445,6 +447,10 @@ struct mul_large_args {
 constexpr uint32_t kLaPerWG = 8;
 constexpr uint32_t kLaMaxLB = 4;
 hipError_t launch_ct_mul_large(const mul_large_args& a, hipStream_t st);
+// a deep sub-batch (mul_large_args::deep) in stages the host can time one by one (k_large_deep.hip):
+// 0 init, 1 the lists kernels, 2 products, 3 the layers kernels, 4 link .. write
+constexpr int kDeepStages = 5;
+hipError_t launch_ct_mul_large_deep(const mul_large_args& a, int stage, hipStream_t st);
 // dense chain images back to hash-order records for the listed pairs whose flag is set (the flag is
 // cleared): pairs = [n_pairs ids, then n_pairs offsets into tmp], tmp holds 3 words per edge of every
 // listed pair (sum of their |A.E|); launches of at most y_cap pairs each (65535: the grid-y limit)
@@ -495,6 +501,7 @@ constexpr uint32_t kCntIShared = 9;   // cnt word: an iblk pair has keys sharing
 constexpr uint32_t kCntDirect = 10;   // cnt word: a direct pair's positions are final (k_large_scan_direct)
 constexpr uint32_t kCntRedo = 11;     // cnt word: a direct pair was handed to the host's redo
 constexpr uint32_t kCntImg = 12;      // cnt word: a direct pair writes C as a dense image (k_large_scan_direct)
+constexpr uint32_t kCntKept = 13;     // cnt word: a deep pair's kept layers (k_large_layers_deep -> its record writer)
 constexpr uint32_t kIblkMaxNB = 63;   // iblk: |B.E| <= 63 (a 64-bit mask per A edge, bit 63 a flag)
 // static bucket groups of key slots [0, S) for one bucket count: head[s] = 0 when s is alone in
 // its bucket, else the first slot + 1 of the bucket's chain; next[s] = the following slot + 1
@@ -504,6 +511,9 @@ hipError_t launch_grp_build(fastmod64 nbm, uint32_t Bm, uint64_t S, uint32_t hbi
 
 hipError_t launch_ct_add(const pvac_ct_batch& A, const pvac_ct_batch& B, pvac_ct_batch& C, int negate_b,
                          uint32_t max_layers, const uint8_t* pair_class, hipStream_t st);
+// the same with the keep / remap table of pair i at slab[C.l_off[i] ..) (k_large_deep.hip): any layer count
+hipError_t launch_ct_add_deep(const pvac_ct_batch& A, const pvac_ct_batch& B, pvac_ct_batch& C, int negate_b,
+                              uint32_t* slab, const uint8_t* pair_class, hipStream_t st);
 
 // ---- ct_lincomb (k_lincomb.hip): segmented sums of optionally scaled ciphers, the work unit the term.
 // Terms of at most kLinWaveLayers layers and kLinWaveEdges edges are closed by a lane group (the

@@ -139,6 +139,7 @@ struct pvac_hip_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     pvac_hip_params prm{};
+    uint32_t layer_limit = PVAC_LAYER_LIMIT_DEFAULT;   // pvac_hip_ctx_set_layer_limit (a chain worker: its parent's)
     std::string err;
     pvhip::dev_buf<uint32_t> nb_table;   // libstdc++ bucket counts and their fastmod64 multipliers
     pvhip::dev_buf<uint64_t> nb_magic;
@@ -170,12 +171,15 @@ struct pvac_hip_ctx {
         uint64_t last_pairs = 0;     // pairs of the last ct_mul_exec (pair_status is valid for these)
         uint64_t redo_total = 0;     // pairs re-run by redo_fresh_pairs since the context was created
         uint64_t path_total[4] = {}; // pair launches: fresh kernel, general path, its iblk order, direct mode
+        uint64_t deep_total = 0;     // ... and of the general path's, the deep kernels (k_large_deep.hip)
     } mul;
     struct {   // the over-budget merge path of ct_add and compact (rt_add.cpp)
         std::vector<pvhip::merge_pair_info> set;     // the latest add or compact plan's items, in pair order
         pvhip::dev_buf<uint8_t> scratch;
         pvhip::dev_buf<unsigned long long> counters;
         pvhip::dev_buf<uint64_t> zero_n;             // zero words: the counts of compact's empty B
+        pvhip::dev_buf<uint32_t> deep_slab;          // k_ct_add_deep: a keep / remap word per layer slot of the plan
+        uint64_t deep_calls = 0;                     // ct_add / ct_sub calls run by k_ct_add_deep
     } merge;
     struct {   // LPN PRF key material (SecKey), enc_value and dec_value scratch (rt_keys.cpp)
         uint64_t k[4] = {0, 0, 0, 0};
@@ -431,6 +435,13 @@ struct step_images {
 // rt_mul.cpp: pvac_hip_ct_mul_exec, with a chain step's images (all null for a caller's batch)
 int ct_mul_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_ct_batch* A, const pvac_ct_batch* B,
                 const uint64_t* nonces, const uint64_t* salts, pvac_ct_batch* C, uint32_t flags, step_images img);
+
+// rt_add.cpp: pvac_hip_ct_add_exec with the most layers a pair may have. The ABI entry passes
+// max(kAddLdsLayers, the context's layer limit); ct_recrypt's and ct_lincomb's sums pass kAddLdsLayers,
+// so their refusals do not move with the limit
+constexpr uint32_t kAddLdsLayers = 30000;   // |A.L| + |B.L| k_ct_add's LDS keep table holds (120 KB)
+int ct_add_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_ct_batch* A, const pvac_ct_batch* B, int negate_b,
+                pvac_ct_batch* C, uint32_t lmax);
 
 // rt_add.cpp, the merge set: the over-budget items ids[0, n) of the plan just made, 8 words each from
 // `gather` (into the device array it is given), turned into c->merge.set in pair order by `decode`

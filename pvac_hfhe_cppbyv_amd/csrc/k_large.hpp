@@ -120,5 +120,9 @@ void launch_large_direct_count(mul_large_args& b, hipStream_t st);
 void launch_large_direct_products(const mul_large_args& b, hipStream_t st);
 // every other pair (k_large_products.hip): k_large_products, k_large_products_la, k_large_products_defer
 void launch_large_products(const mul_large_args& a, hipStream_t st);
+// k_mul_large.hip's stages around the deep kernels (k_large_deep.hip): k_large_init; link, rank, scan,
+// order and write with dynamic bucket chains
+void launch_large_init(const mul_large_args& a, hipStream_t st);
+void launch_large_emit(const mul_large_args& a, hipStream_t st);
 
 }  // namespace pvhip

@@ -40,6 +40,8 @@
 //   products, products_la, products_defer         k_large_products.hip
 //   layers, link, rank, scan, order, write,       here
 //   write_ranges
+// A deep pair (more than kLargeLayersMax layers before compaction: the LDS tables of lists and layers)
+// runs its own lists and layers kernels between these stages (k_large_deep.hip, launch_ct_mul_large_deep).
 // Outside the sequence: static bucket groups, chain images -> records (k_large_aux.hip). Shared
 // device pieces: k_large.hpp; the matrix-core pieces of the products kernels: k_large_mx.hpp.
 #include "k_large.hpp"
@@ -729,8 +731,30 @@ __global__ __launch_bounds__(kLB) void k_large_write_ranges(mul_large_args g) {
 
 }  // namespace
 
+// the stages of this file a deep sub-batch shares with the others (k_large_deep.hip launches its own
+// lists and layers kernels between them): its pairs are never iblk, direct or in a static group
+void launch_large_init(const mul_large_args& a, hipStream_t st) {
+    hipLaunchKernelGGL(k_large_init, dim3(grid_x(a.max_zero > a.max_S ? a.max_zero : a.max_S, kLB * 4, 4096), a.nl),
+                       dim3(kLB), 0, st, a);
+}
+
+void launch_large_emit(const mul_large_args& a, hipStream_t st) {
+    const unsigned nl = a.nl;
+    const unsigned gs = grid_x(a.max_S, kLB * 2, 4096);
+    hipLaunchKernelGGL(k_large_link, dim3(gs, nl), dim3(kLB), 0, st, a);
+    hipLaunchKernelGGL(k_large_rank, dim3(gs, nl), dim3(kLB), 0, st, a);
+    hipLaunchKernelGGL(k_large_scan, dim3(nl), dim3(kLBig), 0, st, a);
+    hipLaunchKernelGGL(k_large_order, dim3(gs, nl), dim3(kLB), 0, st, a);
+    hipLaunchKernelGGL(k_large_write, dim3(grid_x(a.max_capE, kLB * 2, 4096), nl), dim3(kLB), 0, st, a);
+}
+
 hipError_t launch_ct_mul_large(const mul_large_args& a, hipStream_t st) {
     if (!a.nl) return hipSuccess;
+    if (a.deep) {   // (the host runtime launches the stages itself, two of them under their timing names)
+        hipError_t e = hipSuccess;
+        for (int stage = 0; stage < kDeepStages && e == hipSuccess; ++stage) e = launch_ct_mul_large_deep(a, stage, st);
+        return e;
+    }
     if (a.Bm > kBmax || a.max_lay > kLargeLayersMax) return hipErrorInvalidValue;
     const unsigned nl = a.nl;
     hipLaunchKernelGGL(k_large_init, dim3(grid_x(a.max_zero > a.max_S ? a.max_zero : a.max_S, kLB * 4, 4096), nl),

@@ -30,11 +30,16 @@ inline uint32_t ceil_log2(uint64_t x) {
     return b;
 }
 
+// A pair beyond the LDS layer tables of k_large_lists / k_large_layers (accepted only under a raised
+// layer limit, pvac_hip_ctx_set_layer_limit)
+inline bool is_deep(const large_desc& d) { return d.Lc > kLargeLayersMax; }
+
 // Scratch layout of one general-path pair (k_mul_large.hip), offsets relative to 0; the
 // executor rebases them into the arena. 64-bit arrays on even words, 16-byte arrays on
 // multiples of four.
 inline int build_large_desc(large_desc& d, uint64_t pair, uint64_t LA, uint64_t LB, uint64_t nA, uint64_t nB, uint32_t Bm,
-                            std::string& why, bool static_grp = false, bool allow_direct = false) {
+                            std::string& why, bool static_grp = false, bool allow_direct = false,
+                            uint32_t layers_max = kLargeLayersMax) {
     d = large_desc{};
     d.pair = pair;
     d.n = nA * nB;
@@ -45,10 +50,13 @@ inline int build_large_desc(large_desc& d, uint64_t pair, uint64_t LA, uint64_t 
         why = "ct_mul: |A.E||B.E| >= 2^32 products in one pair";
         return PVAC_ENOSYS;
     }
-    if (d.Lc > kLargeLayersMax) {
-        why = "ct_mul: more than " + std::to_string(kLargeLayersMax) + " layers before compaction in one pair";
+    if (d.Lc > layers_max) {
+        why = "ct_mul: more than " + std::to_string(layers_max) + " layers before compaction in one pair";
         return PVAC_ENOSYS;
     }
+    // a deep pair (k_large_deep.hip: its layer tables in global scratch) takes the dynamic route only:
+    // the iblk order, the direct mode and the static groups pack a layer into 15 or 16 bits
+    if (is_deep(d)) static_grp = allow_direct = false;
     if (d.S >= (1ull << 31)) {
         why = "ct_mul: key space |A.L||B.L|B >= 2^31";
         return PVAC_ENOSYS;
@@ -192,6 +200,7 @@ struct sub_batch {
 
 // Cuts the sub-batch that starts at set[i]: pairs are taken while their scratch fits `budget` words,
 // the first one always (a pair larger than the budget runs alone), at most 65,535 (the grid-y limit).
+// Deep pairs get sub-batches of their own (another launch sequence): a sub-batch ends where deepness changes.
 // `set` is left as it is; the out-of-memory split is a second call with a smaller budget.
 inline void cut_sub_batch(const std::vector<large_desc>& set, size_t i, uint64_t budget, sub_batch& out) {
     out.n_iblk = out.n_direct = 0;
@@ -200,7 +209,9 @@ inline void cut_sub_batch(const std::vector<large_desc>& set, size_t i, uint64_t
     a.all_iblk = a.all_direct = 1u;
     uint64_t words = 0;
     size_t j = i;
-    while (j < set.size() && (j == i || words + set[j].words <= budget) && j - i < 65535) words += set[j++].words;
+    const bool deep = i < set.size() && is_deep(set[i]);
+    while (j < set.size() && (j == i || words + set[j].words <= budget) && j - i < 65535 && is_deep(set[j]) == deep)
+        words += set[j++].words;
     out.desc.assign(set.begin() + i, set.begin() + j);
     uint64_t base = 0;
     for (large_desc& d : out.desc) {
@@ -221,17 +232,22 @@ inline void cut_sub_batch(const std::vector<large_desc>& set, size_t i, uint64_t
         out.n_direct += d.direct;
         if (d.direct) a.dir_lb = std::max<uint32_t>(a.dir_lb, d.LB);
         a.max_lay = std::max(a.max_lay, std::max<uint64_t>(d.Lc, (uint64_t)d.LA + d.LB));
+        if (deep) a.max_nA = std::max<uint64_t>(a.max_nA, std::max(d.nA, d.nB));   // (never iblk: see mul_large_args::deep)
     }
+    a.deep = deep ? 1u : 0u;
+    // k_large_products_la's deferred-task list packs an A layer index into 16 bits: a (deep) pair of
+    // 2^16 A layers or more takes one workgroup per task
+    auto la_class = [](const large_desc& d) { return d.LB <= kLaMaxLB && d.LA < (1u << 16); };
     // products: pairs with few B layers (chain steps) take the A-layer-major kernel
     const size_t n = j - i;
     out.sel.resize(n);
     for (size_t k = 0; k < n; ++k)
-        if (out.desc[k].LB <= kLaMaxLB) out.sel[a.n_la++] = (uint32_t)k;
+        if (la_class(out.desc[k])) out.sel[a.n_la++] = (uint32_t)k;
     for (size_t k = 0, q = a.n_la; k < n; ++k) {
         const large_desc& d = out.desc[k];
         const uint64_t tasks = (uint64_t)d.LA * d.LB;
         a.max_tasks_all = std::max(a.max_tasks_all, tasks);
-        if (d.LB <= kLaMaxLB) {
+        if (la_class(d)) {
             a.max_la_wg = std::max<uint64_t>(a.max_la_wg, (d.LA + kLaPerWG - 1) / kLaPerWG);
         } else {
             a.max_tasks = std::max(a.max_tasks, tasks);

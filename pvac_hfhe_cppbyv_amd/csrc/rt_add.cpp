@@ -4,6 +4,7 @@
 
 using namespace pvhip;
 
+
 namespace pvhip {
 
 int merge_gather(pvac_hip_ctx* c, uint64_t n, const std::function<hipError_t(uint64_t*)>& gather,
@@ -89,15 +90,34 @@ int pvac_hip_ct_add_plan(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_
 
 int pvac_hip_ct_add_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_ct_batch* A, const pvac_ct_batch* B,
                          int negate_b, pvac_ct_batch* C) try {
+    return ct_add_exec(c, plan, A, B, negate_b, C, c ? std::max<uint32_t>(kAddLdsLayers, c->layer_limit) : kAddLdsLayers);
+} catch (...) { return caught(c, "ct_add_exec"); }
+
+}  // extern "C"
+
+int pvhip::ct_add_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_ct_batch* A, const pvac_ct_batch* B,
+                       int negate_b, pvac_ct_batch* C, uint32_t lmax) {
     if (!c || !plan || plan->kind != 2 || !batch_ok(A) || !batch_ok(B) || !batch_ok(C))
         return fail(c, PVAC_EINVAL, "ct_add_exec: bad arguments");
     if (A->n != plan->n_pairs || B->n != plan->n_pairs) return fail(c, PVAC_EINVAL, "ct_add_exec: plan mismatch");
     if (!A->n) return PVAC_OK;
-    if (plan->max_layers > 30000) return fail(c, PVAC_ENOSYS, "ct_add_exec: > 30000 layers per cipher");
+    if (plan->max_layers > lmax)
+        return fail(c, PVAC_ENOSYS, "ct_add_exec: > " + std::to_string(lmax) + " layers per cipher");
     // a plan without over-budget pairs reads none of the plan scratch and stays valid
     if (plan->n_large && (!c->ps.is_latest(plan) || plan->n_large != c->merge.set.size()))
         return fail(c, PVAC_EINVAL, "ct_add_exec: plan is not this context's latest plan");
-    {
+    if (plan->max_layers > kAddLdsLayers) {
+        // beyond k_ct_add's LDS table: the whole call on k_ct_add_deep, a slab word per planned layer slot
+        int rc = hip_fail(c, c->merge.deep_slab.grow_floor(std::max<uint64_t>(plan->total_layer_slots, 1)), "alloc ct_add slab");
+        if (rc) return rc;
+        scoped_timer t(c, "ct_add_deep");
+        rc = hip_fail(c,
+                      launch_ct_add_deep(*A, *B, *C, negate_b, c->merge.deep_slab.get(),
+                                         plan->n_large ? c->ps.pair_class.get() : nullptr, c->stream),
+                      "ct_add_deep");
+        if (rc) return rc;
+        ++c->merge.deep_calls;
+    } else {
         scoped_timer t(c, "ct_add");
         const int rc = hip_fail(c,
                                 launch_ct_add(*A, *B, *C, negate_b, plan->max_layers,
@@ -108,7 +128,9 @@ int pvac_hip_ct_add_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_
     if (!plan->n_large) return PVAC_OK;
     scoped_timer t(c, "ct_add_merge");
     return merge_execute(c, *A, *B, *C, negate_b, "ct_add merge");
-} catch (...) { return caught(c, "ct_add_exec"); }
+}
+
+extern "C" {
 
 int pvac_hip_ct_scale(pvac_hip_ctx* c, pvac_ct_batch* X, uint64_t s_lo, uint64_t s_hi) try {
     if (!c || !batch_ok(X)) return PVAC_EINVAL;

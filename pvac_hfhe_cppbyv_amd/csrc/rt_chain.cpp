@@ -384,6 +384,7 @@ int pvac_hip_ct_mul_chain(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac_ch
             if (e != hipSuccess) return hip_fail(c, e, "ct_mul_chain: worker statistics");
             k->worker.arena_cap_words = cap_words;
             k->prm = c->prm;
+            k->layer_limit = c->layer_limit;
             k->worker.spin_us = 200;
             k->worker.img_grid_y = (o->flags & PVAC_CHAIN_IMG_BATCH2) ? 2u : 65535u;
             if (c->powg.get() && (k->powg_n != c->powg_n || !k->powg.get())) {
@@ -419,7 +420,11 @@ int pvac_hip_ct_mul_chain(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac_ch
     const size_t nk = (size_t)D * S;
     std::vector<chain_wstats> ws(nk);
     std::vector<uint64_t> redo0(nk);
-    for (size_t w = 0; w < nk; ++w) redo0[w] = c->chain.kids[w]->mul.redo_total;
+    std::vector<uint64_t> deep0(nk);
+    for (size_t w = 0; w < nk; ++w) {
+        redo0[w] = c->chain.kids[w]->mul.redo_total;
+        deep0[w] = c->chain.kids[w]->mul.deep_total;
+    }
     std::vector<std::thread> th;
     th.reserve(nk);
     try {
@@ -453,6 +458,7 @@ int pvac_hip_ct_mul_chain(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac_ch
         st->gsum_failed += ws[w].gsum_failed;
         st->chunks += ws[w].chunks;
         st->redo += k->mul.redo_total - redo0[w];
+        c->mul.deep_total += k->mul.deep_total - deep0[w];   // pvac_hip_deep_path_count counts the workers' pairs
     }
     st->pair_steps = X->n * o->depth;
     st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

@@ -137,6 +137,28 @@ int pvac_hip_ctx_set_powg(pvac_hip_ctx* c, const uint64_t* powg_host, uint32_t c
     return PVAC_OK;
 } catch (...) { return caught(c, "set_powg"); }
 
+int pvac_hip_ctx_set_layer_limit(pvac_hip_ctx* c, uint32_t max_layers) try {
+    if (!c) return PVAC_EINVAL;
+    if (max_layers < PVAC_LAYER_LIMIT_DEFAULT || max_layers > PVAC_LAYER_LIMIT_MAX)
+        return fail(c, PVAC_EINVAL, "ctx_set_layer_limit: the limit lies in [" + std::to_string(PVAC_LAYER_LIMIT_DEFAULT) + ", " +
+                                        std::to_string(PVAC_LAYER_LIMIT_MAX) + "]");
+    c->layer_limit = max_layers;
+    return PVAC_OK;
+} catch (...) { return caught(c, "ctx_set_layer_limit"); }
+
+int pvac_hip_ctx_layer_limit(pvac_hip_ctx* c, uint32_t* out) {
+    if (!c || !out) return PVAC_EINVAL;
+    *out = c->layer_limit;
+    return PVAC_OK;
+}
+
+int pvac_hip_deep_path_count(pvac_hip_ctx* c, uint64_t out[2]) {
+    if (!c || !out) return PVAC_EINVAL;
+    out[0] = c->mul.deep_total;
+    out[1] = c->merge.deep_calls;
+    return PVAC_OK;
+}
+
 const char* pvac_hip_last_error(pvac_hip_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 int pvac_hip_timing_enable(pvac_hip_ctx* c, int on) try {

@@ -171,7 +171,7 @@ int fold_segments(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac_lincomb* S
             grow_set(1 - cur, ap.total_layer_slots, ap.total_edge_slots);
             if (e != hipSuccess) break;
             rows_of(Cv, 1 - cur);
-            rc = pvac_hip_ct_add_exec(c, &ap, &Av, &Tv, 0, &Cv);
+            rc = ct_add_exec(c, &ap, &Av, &Tv, 0, &Cv, kAddLdsLayers);   // (its 30000-layer refusal stays)
             if (rc) return rc;
             cur ^= 1;
         }

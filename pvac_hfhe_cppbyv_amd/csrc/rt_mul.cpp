@@ -22,7 +22,7 @@ int assign_static_groups(pvac_hip_ctx* c, std::vector<large_desc>& set, bool all
     constexpr uint64_t kMaxWords = 1ull << 28;   // <= 1 GiB of tables
     std::map<uint64_t, uint64_t> cfg;             // bucket count -> max S
     for (const large_desc& d : set)
-        if (d.nbm.d >= 2 * d.S && d.S) {
+        if (d.nbm.d >= 2 * d.S && d.S && !is_deep(d)) {   // a deep pair keeps its dynamic chains
             uint64_t& m = cfg[d.nbm.d];
             m = std::max(m, d.S);
         }
@@ -53,7 +53,7 @@ int assign_static_groups(pvac_hip_ctx* c, std::vector<large_desc>& set, bool all
     }
     for (large_desc& d : set) {
         auto it = off.find(d.nbm.d);
-        if (it == off.end() || d.nbm.d < 2 * d.S || !d.S) continue;
+        if (it == off.end() || d.nbm.d < 2 * d.S || !d.S || is_deep(d)) continue;
         std::string why;
         large_desc x;
         rc = build_large_desc(x, d.pair, d.LA, d.LB, d.nA, d.nB, c->prm.B, why, true,
@@ -82,7 +82,7 @@ int gather_large_descs(pvac_hip_ctx* c, const pvac_ct_batch* A, const pvac_ct_ba
     for (uint64_t k = 0; k < n; ++k) {
         std::string why;
         const int rc = build_large_desc(out[k], info[5 * k], info[5 * k + 1], info[5 * k + 2], info[5 * k + 3],
-                                        info[5 * k + 4], c->prm.B, why);
+                                        info[5 * k + 4], c->prm.B, why, false, false, c->layer_limit);
         if (rc) {
             out.clear();
             return fail(c, rc, why);
@@ -225,7 +225,20 @@ int run_large(pvac_hip_ctx* c, const std::vector<large_desc>& set, const pvac_ct
         a.A_img = img.in;
         a.C_img = img.out;
         a.img_count = img.out ? img.count : nullptr;
-        e = launch_ct_mul_large(a, c->stream);
+        if (a.deep) {
+            // its own lists and layers kernels around the shared stages, each under its timing name
+            for (int stage = 0; stage < kDeepStages && e == hipSuccess; ++stage) {
+                if (stage == 1 || stage == 3) {
+                    scoped_timer t(c, stage == 1 ? "large_lists_deep" : "large_layers_deep");
+                    e = launch_ct_mul_large_deep(a, stage, c->stream);
+                } else {
+                    e = launch_ct_mul_large_deep(a, stage, c->stream);
+                }
+            }
+            if (e == hipSuccess) c->mul.deep_total += sb.end - i;
+        } else {
+            e = launch_ct_mul_large(a, c->stream);
+        }
         if (e != hipSuccess) return hip_fail(c, e, "ct_mul_large");
         c->mul.path_total[1] += sb.end - i;
         c->mul.path_total[2] += sb.n_iblk;

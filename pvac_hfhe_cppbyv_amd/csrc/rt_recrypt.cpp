@@ -337,7 +337,7 @@ int pvac_hip_ct_recrypt_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const p
         Cv.w_lo = buf.w_lo.get();
         Cv.w_hi = buf.w_hi.get();
         Cv.sigma = buf.sigma.get();
-        rc = pvac_hip_ct_add_exec(c, &ap, &Av, &Bv, 0, &Cv);
+        rc = ct_add_exec(c, &ap, &Av, &Bv, 0, &Cv, kAddLdsLayers);   // (its 30000-layer refusal stays)
         if (rc) return rc;
         e = launch_ubk_apply(Cv, c->recrypt.ubk_perm.get(), m_bits, nullptr, c->num_cus, c->stream);
         // the next view: the sums, where ct_add put them
