@@ -12,6 +12,7 @@
 //   keys -> stable sort -> group heads + scan -> group starts -> fold (w) -> sigma-nonzero test
 //   -> keep + scan -> write (meta, w, sigma XOR) -> compact_layers (one block) -> edge relabel.
 #include "common.hpp"
+#include "compact_layers.hpp"
 #include <hipcub/hipcub.hpp>
 
 namespace pvhip {
@@ -132,55 +133,19 @@ constexpr int kLB = 1024;
 __global__ __launch_bounds__(kLB) void k_merge_layers(pvac_ct_batch A, pvac_ct_batch B, pvac_ct_batch C, uint64_t pr,
                                                       const uint64_t* cm, const unsigned long long* nout,
                                                       uint32_t* keep, uint32_t* flag_ident) {
-    __shared__ uint32_t flags[2];
+    __shared__ uint32_t changed;
     __shared__ uint32_t part[kLB / 64];
-    const int tid = threadIdx.x;
-    const uint32_t LA = (uint32_t)A.l_cnt[pr], LB = (uint32_t)B.l_cnt[pr], L = LA + LB;
-    const uint64_t alo = A.l_off[pr], blo = B.l_off[pr], clo = C.l_off[pr];
+    const uint32_t tid = threadIdx.x;
+    const ab_layers src = pair_layers(A, B, pr);
+    const uint32_t L = src.LA + (uint32_t)B.l_cnt[pr];
     const uint64_t ne = *nout;
     for (uint32_t l = tid; l < L; l += kLB) keep[l] = 0;
     __syncthreads();
     for (uint64_t e = tid; e < ne; e += kLB) keep[meta_layer(cm[e])] = 1;   // lids < L by construction
-    __syncthreads();
-    for (;;) {   // transitive PROD parents until stable
-        if (tid == 0) flags[0] = 0;
-        __syncthreads();
-        for (uint32_t l = tid; l < L; l += kLB) {
-            if (!keep[l]) continue;
-            const pvac_layer& x = l < LA ? A.layers[alo + l] : B.layers[blo + (l - LA)];
-            if (x.rule != 1) continue;
-            const uint32_t off = l < LA ? 0u : LA;
-            const uint32_t pa = x.pa + off, pb = x.pb + off;
-            if (pa < L && !keep[pa]) { keep[pa] = 1; flags[0] = 1; }
-            if (pb < L && !keep[pb]) { keep[pb] = 1; flags[0] = 1; }
-        }
-        __syncthreads();
-        if (!flags[0]) break;
-        __syncthreads();
-    }
-    const uint32_t per = (L + kLB - 1) / kLB;
-    uint32_t local = 0;
-    for (uint32_t l = tid * per; l < (tid + 1) * per && l < L; ++l) local += keep[l];
-    uint32_t kept;
-    uint32_t run = block_exclusive_scan<kLB>(local, part, kept);
-    for (uint32_t l = tid * per; l < (tid + 1) * per && l < L; ++l) {
-        const uint32_t k = keep[l];
-        keep[l] = k ? run : 0xFFFFFFFFu;
-        run += k;
-    }
-    __syncthreads();
+    block_close<kLB>(keep, L, &changed, src);
+    const uint32_t kept = block_remap<kLB>(keep, keep, L, part);
     const bool identity = kept == L;
-    for (uint32_t l = tid; l < L; l += kLB) {
-        const uint32_t to = keep[l];
-        if (to == 0xFFFFFFFFu) continue;
-        pvac_layer y = l < LA ? A.layers[alo + l] : B.layers[blo + (l - LA)];
-        if (l >= LA && y.rule == 1) { y.pa += LA; y.pb += LA; }
-        if (!identity && y.rule == 1) {
-            y.pa = y.pa < L ? keep[y.pa] : 0xFFFFFFFFu;
-            y.pb = y.pb < L ? keep[y.pb] : 0xFFFFFFFFu;
-        }
-        C.layers[clo + to] = y;
-    }
+    write_ab_layers<kLB>(src, C.layers + C.l_off[pr], keep, L, identity);
     if (tid == 0) {
         C.l_cnt[pr] = kept;
         C.e_cnt[pr] = ne;

@@ -5,6 +5,7 @@
 #include <cstddef>
 
 #include "common.hpp"
+#include "compact_layers.hpp"
 
 namespace pvhip {
 
@@ -248,117 +249,90 @@ __global__ __launch_bounds__(kScanBlock) void k_scan_apply(scan_arrays a, size_t
 }
 
 // ---------------------------------------------------------------- ct_add / ct_sub
-constexpr int kAddBlock = 256;
+constexpr int kAddBlock = 256;         // keep / remap table in LDS: |A.L| + |B.L| <= 30000
+constexpr int kAddDeepBlock = 1024;    // table in the batch's global slab: any layer count
 
-__global__ __launch_bounds__(kAddBlock) void k_ct_add(pvac_ct_batch A, pvac_ct_batch B, pvac_ct_batch C, int negate_b,
-                                                     uint32_t lds_layers, const uint8_t* pair_class) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    uint32_t* keep = (uint32_t*)lds;                 // [lds_layers] then remap in place
-    __shared__ uint32_t flags[4];
-    __shared__ uint32_t part[kAddBlock / 64];
-    const uint64_t pr = blockIdx.x;
-    if (pr >= A.n) return;
-    if (pair_class && pair_class[pr] == PAIR_LARGE) return;   // over edge_budget: k_add_merge.hip
-    const int tid = threadIdx.x;
-    const uint32_t LA = (uint32_t)A.l_cnt[pr], LB = (uint32_t)B.l_cnt[pr];
-    const uint32_t L = LA + LB;
+// One pair by one workgroup of BS threads: concatenate, shift B's layer ids and PROD parents by
+// |A.L|, compact_layers (compact_layers.hpp) with the keep flags, then the remap, in keep[0, L).
+// kStream: the edge records leave by non-temporal stores (the kernel never rereads them). A call of
+// many pairs gains by it; the deep kernel's one workgroup on 262,000 edges measured 1% slower with it
+// (0.565 against 0.558 ms, profiles/compact_layers), so it keeps plain stores.
+template <int BS, bool kStream>
+__device__ __forceinline__ void ct_add_pair(const pvac_ct_batch& A, const pvac_ct_batch& B, const pvac_ct_batch& C,
+                                            int negate_b, uint64_t pr, uint32_t* keep) {
+    __shared__ uint32_t changed;
+    __shared__ uint32_t part[BS / 64];
+    const uint32_t tid = threadIdx.x;
+    const ab_layers src = pair_layers(A, B, pr);
+    const uint32_t LA = src.LA, L = LA + (uint32_t)B.l_cnt[pr];
     const uint64_t nA = A.e_cnt[pr], nB = B.e_cnt[pr];
-    const uint64_t alo = A.l_off[pr], blo = B.l_off[pr], aeo = A.e_off[pr], beo = B.e_off[pr];
-    const uint64_t clo = C.l_off[pr], ceo = C.e_off[pr];
+    const uint64_t aeo = A.e_off[pr], beo = B.e_off[pr], clo = C.l_off[pr], ceo = C.e_off[pr];
 
-    for (uint32_t l = tid; l < L; l += kAddBlock) keep[l] = 0;
-    if (tid == 0) { flags[0] = 0; flags[1] = 0; }
+    for (uint32_t l = tid; l < L; l += BS) keep[l] = 0;
     __syncthreads();
     // used by edges (encrypt.hpp:78)
-    for (uint64_t e = tid; e < nA; e += kAddBlock) {
+    for (uint64_t e = tid; e < nA; e += BS) {
         const uint32_t lid = meta_layer(A.meta[aeo + e]);
         if (lid < L) keep[lid] = 1;
     }
-    for (uint64_t e = tid; e < nB; e += kAddBlock) {
+    for (uint64_t e = tid; e < nB; e += BS) {
         const uint32_t lid = meta_layer(B.meta[beo + e]) + LA;
         if (lid < L) keep[lid] = 1;
     }
-    __syncthreads();
-    // transitive closure over PROD parents, parallel sweeps until stable
-    for (;;) {
-        if (tid == 0) flags[0] = 0;
-        __syncthreads();
-        for (uint32_t l = tid; l < L; l += kAddBlock) {
-            if (!keep[l]) continue;
-            const pvac_layer& x = l < LA ? A.layers[alo + l] : B.layers[blo + (l - LA)];
-            if (x.rule != 1) continue;
-            const uint32_t off = l < LA ? 0u : LA;
-            const uint32_t pa = x.pa + off, pb = x.pb + off;
-            if (pa < L && !keep[pa]) { keep[pa] = 1; flags[0] = 1; }
-            if (pb < L && !keep[pb]) { keep[pb] = 1; flags[0] = 1; }
-        }
-        __syncthreads();
-        if (!flags[0]) break;
-        __syncthreads();
-    }
-    // remap = exclusive count of kept layers (chunked block scan)
-    const uint32_t per = (L + kAddBlock - 1) / kAddBlock;
-    uint32_t local = 0;
-    for (uint32_t l = tid * per; l < (tid + 1) * per && l < L; ++l) local += keep[l];
-    uint32_t kept;
-    uint32_t run = block_exclusive_scan<kAddBlock>(local, part, kept);
-    for (uint32_t l = tid * per; l < (tid + 1) * per && l < L; ++l) {
-        const uint32_t k = keep[l];
-        keep[l] = k ? run : 0xFFFFFFFFu;
-        run += k;
-    }
-    __syncthreads();
+    block_close<BS>(keep, L, &changed, src);
+    const uint32_t kept = block_remap<BS>(keep, keep, L, part);
     const bool identity = kept == L;
-    // layers
-    for (uint32_t l = tid; l < L; l += kAddBlock) {
-        const uint32_t to = keep[l];
-        if (to == 0xFFFFFFFFu) continue;
-        pvac_layer y = l < LA ? A.layers[alo + l] : B.layers[blo + (l - LA)];
-        if (l >= LA && y.rule == 1) { y.pa += LA; y.pb += LA; }
-        if (!identity && y.rule == 1) {
-            y.pa = y.pa < L ? keep[y.pa] : 0xFFFFFFFFu;
-            y.pb = y.pb < L ? keep[y.pb] : 0xFFFFFFFFu;
-        }
-        C.layers[clo + to] = y;
-    }
+    write_ab_layers<BS>(src, C.layers + clo, keep, L, identity);
     if (tid == 0) {
         C.l_cnt[pr] = kept;
         C.e_cnt[pr] = nA + nB;
     }
     // edges (concat; B shifted and optionally scaled by p-1)
     const fp pm1{kAll - 1, kM63};
-    for (uint64_t e = tid; e < nA + nB; e += kAddBlock) {
+    for (uint64_t e = tid; e < nA + nB; e += BS) {
         const bool fromB = e >= nA;
-        const uint64_t src = fromB ? beo + (e - nA) : aeo + e;
-        uint64_t m = fromB ? B.meta[src] : A.meta[src];
-        uint64_t wl = fromB ? B.w_lo[src] : A.w_lo[src];
-        uint64_t wh = fromB ? B.w_hi[src] : A.w_hi[src];
+        const uint64_t s = fromB ? beo + (e - nA) : aeo + e;
+        uint64_t m = fromB ? B.meta[s] : A.meta[s];
+        uint64_t wl = fromB ? B.w_lo[s] : A.w_lo[s];
+        uint64_t wh = fromB ? B.w_hi[s] : A.w_hi[s];
         uint32_t lid = meta_layer(m) + (fromB ? LA : 0u);
-        if (!identity) lid = lid < L ? keep[lid] : 0xFFFFFFFFu;
+        if (!identity) lid = lid < L ? keep[lid] : kDropped;
         m = (m & ~0xFFFFFFFFull) | lid;
         if (fromB && negate_b) {
             const fp r = fp_mul(fp{wl, wh}, pm1);
             wl = r.lo; wh = r.hi;
         }
-        __builtin_nontemporal_store((unsigned long long)m, (unsigned long long*)C.meta + ceo + e);
-        __builtin_nontemporal_store((unsigned long long)wl, (unsigned long long*)C.w_lo + ceo + e);
-        __builtin_nontemporal_store((unsigned long long)wh, (unsigned long long*)C.w_hi + ceo + e);
-    }
-    // sigma carry: one 16-byte lane chunk per work item
-    if (C.sigma && A.sigma && B.sigma) {
-        const uint32_t sw = C.sigma_words;
-        const uint64_t chunks_per_edge = sw / 2;
-        const uint64_t total = (nA + nB) * chunks_per_edge;
-        for (uint64_t c = tid; c < total; c += kAddBlock) {
-            const uint64_t e = c / chunks_per_edge, k = c - e * chunks_per_edge;
-            const bool fromB = e >= nA;
-            const ulonglong2* srcp = fromB ? (const ulonglong2*)(B.sigma + (beo + (e - nA)) * B.sigma_words)
-                                           : (const ulonglong2*)(A.sigma + (aeo + e) * A.sigma_words);
-            ((ulonglong2*)(C.sigma + (ceo + e) * sw))[k] = srcp[k];
+        if (kStream) {
+            __builtin_nontemporal_store((unsigned long long)m, (unsigned long long*)C.meta + ceo + e);
+            __builtin_nontemporal_store((unsigned long long)wl, (unsigned long long*)C.w_lo + ceo + e);
+            __builtin_nontemporal_store((unsigned long long)wh, (unsigned long long*)C.w_hi + ceo + e);
+        } else {
+            C.meta[ceo + e] = m;
+            C.w_lo[ceo + e] = wl;
+            C.w_hi[ceo + e] = wh;
         }
     }
+    carry_sigma_rows(A, B, C, aeo, beo, ceo, nA, nB, tid, BS);
 }
 
+// a pair over edge_budget is k_add_merge.hip's
+__device__ __forceinline__ bool add_pair_live(const pvac_ct_batch& A, const uint8_t* pair_class, uint64_t pr) {
+    return pr < A.n && !(pair_class && pair_class[pr] == PAIR_LARGE);
+}
+
+__global__ __launch_bounds__(kAddBlock) void k_ct_add(pvac_ct_batch A, pvac_ct_batch B, pvac_ct_batch C, int negate_b,
+                                                     const uint8_t* pair_class) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];   // [max |A.L| + |B.L|] words
+    if (add_pair_live(A, pair_class, blockIdx.x)) ct_add_pair<kAddBlock, true>(A, B, C, negate_b, blockIdx.x, (uint32_t*)lds);
+}
+
+// the table at slab[C.l_off[pair] ..): C.l_off is the exclusive scan of |A.L| + |B.L|, so one slab of
+// the plan's total_layer_slots words serves the batch
+__global__ __launch_bounds__(kAddDeepBlock) void k_ct_add_deep(pvac_ct_batch A, pvac_ct_batch B, pvac_ct_batch C,
+                                                              int negate_b, uint32_t* slab, const uint8_t* pair_class) {
+    if (add_pair_live(A, pair_class, blockIdx.x))
+        ct_add_pair<kAddDeepBlock, false>(A, B, C, negate_b, blockIdx.x, slab + C.l_off[blockIdx.x]);
+}
 
 // Pairs of at most 64 layers (every fresh and most chain ciphers): a group of G lanes per pair,
 // G = 64 (one wave) or 32 (two pairs per wave, for pairs of at most 32 layers: twice the pairs in
@@ -369,13 +343,6 @@ __global__ __launch_bounds__(kAddBlock) void k_ct_add(pvac_ct_batch A, pvac_ct_b
 // edges and ran at 14% of the HBM roofline.
 constexpr int kAddWaves = 4;
 constexpr int kPre = 3;   // edges per lane held in registers by k_ct_add_wave (fresh pairs: all)
-
-template <int G>
-__device__ __forceinline__ uint64_t group_or_u64(uint64_t v) {
-#pragma unroll
-    for (int d = 1; d < G; d <<= 1) v |= (uint64_t)__shfl_xor((long long)v, d, 64);
-    return v;
-}
 
 template <int G>
 __global__ __launch_bounds__(64 * kAddWaves) void k_ct_add_wave(pvac_ct_batch A, pvac_ct_batch B, pvac_ct_batch C,
@@ -431,26 +398,17 @@ __global__ __launch_bounds__(64 * kAddWaves) void k_ct_add_wave(pvac_ct_batch A,
     const uint32_t off = l < LA ? 0u : LA;
     const uint32_t pa = x.pa + off, pb = x.pb + off;
     const uint64_t mypm = (l < L && x.rule == 1) ? ((pa < L ? 1ull << pa : 0ull) | (pb < L ? 1ull << pb : 0ull)) : 0ull;
-    uint64_t keep = used;
-    for (;;) {   // depth-bounded by L; the wave stops when every group has reached its fixpoint
-        const uint64_t nk = keep | group_or_u64<G>(((keep >> l) & 1ull) ? mypm : 0ull);
-        const bool moved = nk != keep;
-        keep = nk;
-        if (!__any(moved)) break;
-    }
+    const uint64_t keep = group_close<G>(used, mypm, l);
     const uint32_t kept = (uint32_t)__popcll(keep);
     const bool identity = kept == L;
-    const uint32_t to = ((keep >> l) & 1ull) ? (uint32_t)__popcll(keep & ((1ull << l) - 1ull)) : 0xFFFFFFFFu;
+    const uint32_t to = ((keep >> l) & 1ull) ? (uint32_t)__popcll(keep & ((1ull << l) - 1ull)) : kDropped;
     uint32_t* remap = remap_s[wave] + ((uint32_t)lane & ~(uint32_t)(G - 1));
     remap[l] = to;
     __builtin_amdgcn_wave_barrier();
-    if (l < L && to != 0xFFFFFFFFu) {
+    if (l < L && to != kDropped) {
         pvac_layer y = x;
         if (l >= LA && y.rule == 1) { y.pa += LA; y.pb += LA; }
-        if (!identity && y.rule == 1) {
-            y.pa = y.pa < L ? remap[y.pa] : 0xFFFFFFFFu;
-            y.pb = y.pb < L ? remap[y.pb] : 0xFFFFFFFFu;
-        }
+        remap_parents(y, remap, L, identity);
         C.layers[clo + to] = y;
     }
     if (live && gl == 0) {
@@ -462,7 +420,7 @@ __global__ __launch_bounds__(64 * kAddWaves) void k_ct_add_wave(pvac_ct_batch A,
     auto emit = [&](uint64_t e, uint64_t m, uint64_t wl, uint64_t wh) {
         const bool fromB = e >= nA;
         uint32_t lid = meta_layer(m) + (fromB ? LA : 0u);
-        if (!identity) lid = lid < L ? remap[lid] : 0xFFFFFFFFu;
+        if (!identity) lid = lid < L ? remap[lid] : kDropped;
         m = (m & ~0xFFFFFFFFull) | lid;
         if (fromB && negate_b) {
             const fp r = fp_mul(fp{wl, wh}, pm1);
@@ -484,18 +442,7 @@ __global__ __launch_bounds__(64 * kAddWaves) void k_ct_add_wave(pvac_ct_batch A,
         emit(e, fromB ? B.meta[src] : A.meta[src], fromB ? B.w_lo[src] : A.w_lo[src],
              fromB ? B.w_hi[src] : A.w_hi[src]);
     }
-    if (C.sigma && A.sigma && B.sigma) {   // sigma carry: 16 bytes per lane
-        const uint32_t sw = C.sigma_words;
-        const uint64_t chunks_per_edge = sw / 2;
-        const uint64_t total = (nA + nB) * chunks_per_edge;
-        for (uint64_t c = gl; c < total; c += G) {
-            const uint64_t e = c / chunks_per_edge, k = c - e * chunks_per_edge;
-            const bool fromB = e >= nA;
-            const ulonglong2* srcp = fromB ? (const ulonglong2*)(B.sigma + (beo + (e - nA)) * B.sigma_words)
-                                           : (const ulonglong2*)(A.sigma + (aeo + e) * A.sigma_words);
-            ((ulonglong2*)(C.sigma + (ceo + e) * sw))[k] = srcp[k];
-        }
-    }
+    carry_sigma_rows(A, B, C, aeo, beo, ceo, nA, nB, gl, G);
 }
 
 }  // namespace
@@ -574,8 +521,15 @@ hipError_t launch_ct_add(const pvac_ct_batch& A, const pvac_ct_batch& B, pvac_ct
     }
     const size_t lds = ((size_t)max_layers * 4 + 15) & ~(size_t)15;
     if (lds > 120 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_ct_add, dim3((unsigned)A.n), dim3(kAddBlock), lds, st, A, B, C, negate_b, max_layers,
-                       pair_class);
+    hipLaunchKernelGGL(k_ct_add, dim3((unsigned)A.n), dim3(kAddBlock), lds, st, A, B, C, negate_b, pair_class);
+    return hipGetLastError();
+}
+
+hipError_t launch_ct_add_deep(const pvac_ct_batch& A, const pvac_ct_batch& B, pvac_ct_batch& C, int negate_b,
+                              uint32_t* slab, const uint8_t* pair_class, hipStream_t st) {
+    if (!A.n) return hipSuccess;
+    if (!slab || A.n > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_ct_add_deep, dim3((unsigned)A.n), dim3(kAddDeepBlock), 0, st, A, B, C, negate_b, slab, pair_class);
     return hipGetLastError();
 }
 

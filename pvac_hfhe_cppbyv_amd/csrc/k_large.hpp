@@ -1,8 +1,9 @@
 // k_large.hpp — device-side pieces of the general ct_mul path that at least two of its kernel files
-// use (k_mul_large.hip, k_large_products.hip, k_large_direct.hip, k_large_aux.hip); included only by
-// them. The host-visible interface is in common.hpp.
+// use (k_mul_large.hip, k_large_products.hip, k_large_direct.hip, k_large_aux.hip, k_large_deep.hip);
+// included only by them. The host-visible interface is in common.hpp.
 #pragma once
 #include "common.hpp"
+#include "sha256.hpp"
 
 #ifdef PVAC_DIR_STAMPS   // diagnostic build only: the direct kernels' wave 0 s_memtime per phase (k_large_direct.hip)
 __device__ __forceinline__ unsigned long long dir_stamp() {
@@ -73,8 +74,49 @@ __device__ __forceinline__ layer_src side_layer(const pvac_ct_batch* X, uint64_t
     return layer_src{X, eo, S + o_lst + 2u * L + S[o_lst + l], S[o_lst + L + l]};
 }
 
+// ---------------------------------------------------------------- layers
+// A pair's uncompacted layer list A || B || products (|A.L| + |B.L| + |A.L||B.L| entries): B's PROD
+// parents shifted by |A.L|, product layer lp = la |B.L| + lb a PROD of la and |A.L| + lb. Both are for
+// the files that run compact_layers over the list (k_mul_large.hip, k_large_deep.hip).
+__device__ __forceinline__ void layer_parents(const mul_large_args& g, uint64_t alo, uint64_t blo, uint32_t LA,
+                                              uint32_t LB, uint32_t l, uint32_t& rule, uint32_t& pa, uint32_t& pb) {
+    const uint32_t base = LA + LB;
+    if (l < LA) {
+        const pvac_layer& x = g.A.layers[alo + l];
+        rule = x.rule; pa = x.pa; pb = x.pb;
+    } else if (l < base) {
+        const pvac_layer& x = g.B.layers[blo + (l - LA)];
+        rule = x.rule; pa = x.pa + LA; pb = x.pb + LA;
+    } else {
+        rule = 1; pa = (l - base) / LB; pb = LA + (l - base) % LB;
+    }
+}
+
+// layer l's record before the remap; a product layer's nonce is the one drawn for its slot of C, its
+// ztag is computed here (so only for the layers a caller keeps)
+__device__ __forceinline__ pvac_layer layer_record(const mul_large_args& g, uint64_t alo, uint64_t blo, uint64_t clo,
+                                                   uint32_t LA, uint32_t LB, uint32_t l) {
+    const uint32_t base = LA + LB;
+    pvac_layer y;
+    if (l < LA) {
+        y = g.A.layers[alo + l];
+    } else if (l < base) {
+        y = g.B.layers[blo + (l - LA)];
+        if (y.rule == 1) { y.pa += LA; y.pb += LA; }
+    } else {
+        const uint32_t lp = l - base;
+        const uint64_t slot = clo + l;
+        y.rule = 1; y.pad = 0;
+        y.pa = lp / LB; y.pb = LA + lp % LB;
+        y.nonce_lo = g.nonces[2 * slot];
+        y.nonce_hi = g.nonces[2 * slot + 1];
+        y.ztag = layer_ztag(g.canon_tag, y.nonce_lo, y.nonce_hi);
+    }
+    return y;
+}
+
 // ---------------------------------------------------------------- products
-constexpr int kLP = 384;                 // products workgroup: one lane per output index r (B = 337)
+constexpr int kLP = 384;                // products workgroup: one lane per output index r (B = 337)
 constexpr int kLPX = 256;                // products workgroup with the matrix-core dense mode (4 waves)
 constexpr int kLaMinBlocks = 4;          // resident workgroups per CU the A-layer-major kernels are compiled for
 constexpr int kLPRows = 3;               // B <= kLP * kLPRows

@@ -20,13 +20,14 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "compact_layers.hpp"
 
 namespace pvhip {
 
 namespace {
 
 constexpr int kLinBlock = 256;
-constexpr uint32_t kNone = 0xFFFFFFFFu;
+constexpr uint32_t kNone = kDropped;   // map_layer: dropped, or not one of the term's layers
 constexpr uint32_t kTileTerms = 256;   // terms of an edge tile whose records are staged in LDS
 
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
@@ -43,13 +44,6 @@ __device__ __forceinline__ void wave_max_if_greater(unsigned int* p, uint32_t v)
         v = o > v ? o : v;
     }
     if ((threadIdx.x & 63u) == 0 && v > __atomic_load_n(p, __ATOMIC_RELAXED)) atomicMax(p, v);
-}
-
-template <int G>
-__device__ __forceinline__ uint64_t group_or_u64(uint64_t v) {
-#pragma unroll
-    for (int d = 1; d < G; d <<= 1) v |= (uint64_t)__shfl_xor((long long)v, d, 64);
-    return v;
 }
 
 // the last index in [lo, hi) whose entry is <= v (s non-decreasing with s[lo] <= v; any other
@@ -86,7 +80,7 @@ __device__ __forceinline__ term_head load_head(const lincomb_args& a, uint64_t k
 __device__ __forceinline__ bool wave_route(const term_head& h) { return h.L <= kLinWaveLayers && h.E <= kLinWaveEdges; }
 
 // One term per group of G lanes (G = 32: two terms per wave, both of at most 32 layers). Lane l holds
-// layer l's PROD parents; the closure is k_ct_add_wave's. A dead group (tail, bad index, a term of
+// layer l's PROD parents; the closure is compact_layers.hpp's wave form. A dead group (tail, bad index, a term of
 // the workgroup route) runs with zero counts, so every group reaches the same shuffles.
 template <int G>
 __device__ __forceinline__ void plan_term(const lincomb_args& a, uint64_t k, bool live, const term_head& h) {
@@ -114,13 +108,7 @@ __device__ __forceinline__ void plan_term(const lincomb_args& a, uint64_t k, boo
     // transitive PROD parents (encrypt.hpp:80-88)
     const uint64_t mypm =
         (gl < Lw && rule == 1) ? ((pa < Lw ? 1ull << pa : 0ull) | (pb < Lw ? 1ull << pb : 0ull)) : 0ull;
-    uint64_t keep = used;
-    for (;;) {
-        const uint64_t nk = keep | group_or_u64<G>(((keep >> gl) & 1ull) ? mypm : 0ull);
-        const bool moved = nk != keep;
-        keep = nk;
-        if (!__any(moved)) break;
-    }
+    const uint64_t keep = group_close<G>(used, mypm, gl);
     // a kept PROD layer whose parent is not one of the term's layers (remap[pa] out of range there)
     if (gl < Lw && ((keep >> gl) & 1ull) && rule == 1 && (pa >= Lw || pb >= Lw)) bad = 1;
     bad = group_or_u64<G>(bad);
@@ -182,12 +170,12 @@ __global__ __launch_bounds__(kLinBlock) void k_lincomb_index(lincomb_args a) {
     }
 }
 
-// The workgroup route: one term per workgroup, k_ct_add's keep table in LDS (its index checks are the
-// contract flag here). Needs the scanned sL: the term's remap table lies at sL[k].
+// The workgroup route: one term per workgroup, compact_layers.hpp's workgroup form on a keep table in LDS
+// (k_ct_add's index checks are the contract flag here). Needs the scanned sL: the term's remap table lies at sL[k].
 __global__ __launch_bounds__(kLinBlock) void k_lincomb_plan_wg(lincomb_args a, uint64_t n_wg) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     uint32_t* keep = (uint32_t*)lds;
-    __shared__ uint32_t flags[2];   // [0] a sweep marked a layer, [1] out of contract
+    __shared__ uint32_t changed, bad;   // a sweep marked a layer; the term is out of contract
     __shared__ uint32_t part[kLinBlock / 64];
     const pvac_ct_batch& X = a.X;
     const uint32_t tid = threadIdx.x;
@@ -195,45 +183,23 @@ __global__ __launch_bounds__(kLinBlock) void k_lincomb_plan_wg(lincomb_args a, u
         const uint64_t k = a.wg_ids[w];
         const uint64_t t = a.term[k];
         const uint32_t L = (uint32_t)X.l_cnt[t];   // <= kLinMaxLayers (host-checked)
-        const uint64_t E = X.e_cnt[t], xlo = X.l_off[t], xeo = X.e_off[t];
+        const uint64_t E = X.e_cnt[t], xeo = X.e_off[t];
+        const pvac_layer* lay = X.layers + X.l_off[t];
         for (uint32_t l = tid; l < L; l += kLinBlock) keep[l] = 0;
-        if (tid == 0) flags[1] = 0;
+        if (tid == 0) bad = 0;
         __syncthreads();
         for (uint64_t e = tid; e < E; e += kLinBlock) {
             const uint32_t lid = meta_layer(X.meta[xeo + e]);
             if (lid < L) keep[lid] = 1;
-            else flags[1] = 1;
+            else bad = 1;
         }
-        __syncthreads();
-        for (;;) {   // parallel sweeps until stable
-            if (tid == 0) flags[0] = 0;
-            __syncthreads();
-            for (uint32_t l = tid; l < L; l += kLinBlock) {
-                if (!keep[l]) continue;
-                const pvac_layer* y = X.layers + xlo + l;
-                if (y->rule != 1) continue;
-                const uint32_t pa = y->pa, pb = y->pb;
-                if (pa >= L || pb >= L) flags[1] = 1;
-                if (pa < L && !keep[pa]) { keep[pa] = 1; flags[0] = 1; }
-                if (pb < L && !keep[pb]) { keep[pb] = 1; flags[0] = 1; }
-            }
-            __syncthreads();
-            if (!flags[0]) break;
-            __syncthreads();
-        }
-        const uint32_t per = (L + kLinBlock - 1) / kLinBlock;
-        uint32_t local = 0;
-        for (uint32_t l = tid * per; l < (tid + 1) * per && l < L; ++l) local += keep[l];
-        uint32_t kept;
-        uint32_t run = block_exclusive_scan<kLinBlock>(local, part, kept);
-        uint32_t* remap = a.remap + a.sL[k];
-        for (uint32_t l = tid * per; l < (tid + 1) * per && l < L; ++l) {
-            const uint32_t kp = keep[l];
-            remap[l] = kp ? run : kNone;
-            run += kp;
-        }
-        if (tid == 0) a.kraw[k] = (uint64_t)kept | ((uint64_t)flags[1] << 40);
-        __syncthreads();   // keep[] and flags[] are the next term's
+        block_close<kLinBlock>(keep, L, &changed, [&](uint32_t l, uint32_t& rule, uint32_t& pa, uint32_t& pb) {
+            rule = lay[l].rule; pa = lay[l].pa; pb = lay[l].pb;
+            if (rule == 1 && (pa >= L || pb >= L)) bad = 1;   // a kept PROD layer with a parent beyond the term
+        });
+        // the remap to scratch; its closing barrier also frees keep[] and bad for the next term
+        const uint32_t kept = block_remap<kLinBlock>(keep, a.remap + a.sL[k], L, part);
+        if (tid == 0) a.kraw[k] = (uint64_t)kept | ((uint64_t)bad << 40);
     }
 }
 

@@ -44,8 +44,8 @@
 // runs its own lists and layers kernels between these stages (k_large_deep.hip, launch_ct_mul_large_deep).
 // Outside the sequence: static bucket groups, chain images -> records (k_large_aux.hip). Shared
 // device pieces: k_large.hpp; the matrix-core pieces of the products kernels: k_large_mx.hpp.
+#include "compact_layers.hpp"
 #include "k_large.hpp"
-#include "sha256.hpp"
 
 namespace pvhip {
 
@@ -207,20 +207,6 @@ __global__ __launch_bounds__(kLBig) void k_large_lists(mul_large_args g) {
 // One workgroup per pair (encrypt.hpp:73-104): keep = product layers with emitted edges, plus
 // transitive PROD parents; remap by exclusive count; write the kept records (product-layer
 // ztags computed here, only for kept layers) and leave the remap in scratch for the writer.
-__device__ __forceinline__ void layer_parents(const mul_large_args& g, uint64_t alo, uint64_t blo, uint32_t LA,
-                                              uint32_t LB, uint32_t l, uint32_t& rule, uint32_t& pa, uint32_t& pb) {
-    const uint32_t base = LA + LB;
-    if (l < LA) {
-        const pvac_layer& x = g.A.layers[alo + l];
-        rule = x.rule; pa = x.pa; pb = x.pb;
-    } else if (l < base) {
-        const pvac_layer& x = g.B.layers[blo + (l - LA)];
-        rule = x.rule; pa = x.pa + LA; pb = x.pb + LA;
-    } else {
-        rule = 1; pa = (l - base) / LB; pb = LA + (l - base) % LB;
-    }
-}
-
 __global__ __launch_bounds__(kLBig) void k_large_layers(mul_large_args g) {
     extern __shared__ __attribute__((aligned(16))) uint32_t keep[];   // [Lc]
     __shared__ uint32_t changed;
@@ -238,57 +224,17 @@ __global__ __launch_bounds__(kLBig) void k_large_layers(mul_large_args g) {
     if (d.iblk && S[d.o_cnt + kCntIFail])   // k_large_rank marks this pair's leaders next
         for (uint64_t w = tid; w < 2 * d.nblk; w += kLBig) S[d.o_bmask + w] = 0;
     for (uint32_t l = tid; l < Lc; l += kLBig) keep[l] = l >= base ? (used[l] != 0) : 0u;
-    for (;;) {
-        __syncthreads();
-        if (tid == 0) changed = 0;
-        __syncthreads();
-        for (uint32_t l = tid; l < Lc; l += kLBig) {
-            if (!keep[l]) continue;
-            uint32_t rule, pa, pb;
-            layer_parents(g, alo, blo, LA, LB, l, rule, pa, pb);
-            if (rule != 1) continue;
-            if (pa < Lc && !keep[pa]) { keep[pa] = 1; changed = 1; }
-            if (pb < Lc && !keep[pb]) { keep[pb] = 1; changed = 1; }
-        }
-        __syncthreads();
-        if (!changed) break;
-    }
-    // remap = exclusive count of kept layers (chunked block scan)
-    const uint32_t per = (Lc + kLBig - 1) / kLBig;
-    uint32_t local = 0;
-    for (uint32_t l = tid * per; l < (tid + 1) * per && l < Lc; ++l) local += keep[l];
-    uint32_t kept;
-    uint32_t run = block_exclusive_scan<kLBig>(local, part, kept);
-    for (uint32_t l = tid * per; l < (tid + 1) * per && l < Lc; ++l) {
-        const uint32_t k = keep[l];
-        keep[l] = k ? run : kInf;
-        run += k;
-    }
-    __syncthreads();
+    block_close<kLBig>(keep, Lc, &changed, [&](uint32_t l, uint32_t& rule, uint32_t& pa, uint32_t& pb) {
+        layer_parents(g, alo, blo, LA, LB, l, rule, pa, pb);
+    });
+    const uint32_t kept = block_remap<kLBig>(keep, keep, Lc, part);
     const bool identity = kept == Lc;
     for (uint32_t l = tid; l < Lc; l += kLBig) {
         const uint32_t to = keep[l];
         used[l] = to;   // remap for the edge writer
-        if (to == kInf) continue;
-        pvac_layer y;
-        if (l < LA) {
-            y = g.A.layers[alo + l];
-        } else if (l < base) {
-            y = g.B.layers[blo + (l - LA)];
-            if (y.rule == 1) { y.pa += LA; y.pb += LA; }
-        } else {
-            const uint32_t lp = l - base;
-            const uint64_t slot = clo + l;
-            y.rule = 1; y.pad = 0;
-            y.pa = lp / LB; y.pb = LA + lp % LB;
-            y.nonce_lo = g.nonces[2 * slot];
-            y.nonce_hi = g.nonces[2 * slot + 1];
-            y.ztag = layer_ztag(g.canon_tag, y.nonce_lo, y.nonce_hi);
-        }
-        if (!identity && y.rule == 1) {
-            y.pa = y.pa < Lc ? keep[y.pa] : kInf;
-            y.pb = y.pb < Lc ? keep[y.pb] : kInf;
-        }
+        if (to == kDropped) continue;
+        pvac_layer y = layer_record(g, alo, blo, clo, LA, LB, l);
+        remap_parents(y, keep, Lc, identity);
         g.C.layers[clo + to] = y;
     }
     if (tid == 0) g.C.l_cnt[pr] = kept;

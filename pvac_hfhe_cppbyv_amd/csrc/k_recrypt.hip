@@ -5,6 +5,7 @@
 //                     workgroup per cipher whose key space |L| 2B fits kCompactSmallCells LDS words
 // A cipher above the bound takes launch_add_merge with an empty B (k_add_merge.hip).
 #include "common.hpp"
+#include "compact_layers.hpp"
 
 #include <algorithm>
 
@@ -264,7 +265,6 @@ __global__ __launch_bounds__(kCsBlock) void k_compact_small(pvac_ct_batch X, pva
     }
     const uint32_t K = L * 2u * Bm, G = (K + 63u) / 64u;
     volatile uint32_t* vcell = cell;
-    volatile uint32_t* vlay = lay;
     for (uint32_t c = tid; c < G * 64u; c += kCsBlock) cell[c] = kCsNone;
     for (uint32_t l = tid; l < L; l += kCsBlock) lay[l] = 0;
     __syncthreads();
@@ -297,48 +297,28 @@ __global__ __launch_bounds__(kCsBlock) void k_compact_small(pvac_ct_batch X, pva
         }
         if (keep) {
             cell[c] = v | kCsKeep;
-            vlay[c / (2u * Bm)] = 1;
+            lay[c / (2u * Bm)] = 1;
         }
         const uint64_t km = __ballot(keep);
         if (lane == 0) gbase[g] = (uint32_t)__popcll(km);
     }
     __syncthreads();
     // 3. compact_layers (encrypt.hpp:73-104): PROD parents of used layers until stable, then the remap
-    for (;;) {
-        if (tid == 0) changed = 0;
-        __syncthreads();
-        for (uint32_t l = tid; l < L; l += kCsBlock) {
-            if (!vlay[l]) continue;
-            const pvac_layer& y = X.layers[xlo + l];
-            if (y.rule != 1) continue;
-            if (y.pa < L && !vlay[y.pa]) { vlay[y.pa] = 1; changed = 1; }
-            if (y.pb < L && !vlay[y.pb]) { vlay[y.pb] = 1; changed = 1; }
-        }
-        __syncthreads();
-        if (!changed) break;
-        __syncthreads();
-    }
-    const uint32_t per = (L + kCsBlock - 1) / kCsBlock;
-    uint32_t local = 0;
-    for (uint32_t l = tid * per; l < (tid + 1) * per && l < L; ++l) local += lay[l];
-    uint32_t kept;
-    uint32_t run = block_exclusive_scan<kCsBlock>(local, part, kept);
-    for (uint32_t l = tid * per; l < (tid + 1) * per && l < L; ++l) {
-        const uint32_t k = lay[l];
-        lay[l] = k ? run : 0xFFFFFFFFu;
-        run += k;
-    }
-    __syncthreads();
+    const pvac_layer* xl = X.layers + xlo;
+    block_close<kCsBlock>(lay, L, &changed, [&](uint32_t l, uint32_t& rule, uint32_t& pa, uint32_t& pb) {
+        rule = xl[l].rule; pa = xl[l].pa; pb = xl[l].pb;
+    });
+    const uint32_t kept = block_remap<kCsBlock>(lay, lay, L, part);
     const bool identity = kept == L;
     for (uint32_t l = tid; l < L; l += kCsBlock) {
         const uint32_t to = lay[l];
-        if (to == 0xFFFFFFFFu) continue;
-        const pvac_layer& y = X.layers[xlo + l];   // field by field: a local copy of the record goes to scratch
+        if (to == kDropped) continue;
+        const pvac_layer& y = xl[l];   // field by field: a local copy of the record goes to scratch
         pvac_layer& z = C.layers[clo + to];
         uint32_t pa = y.pa, pb = y.pb;
         if (!identity && y.rule == 1) {
-            pa = pa < L ? lay[pa] : 0xFFFFFFFFu;
-            pb = pb < L ? lay[pb] : 0xFFFFFFFFu;
+            pa = pa < L ? lay[pa] : kDropped;
+            pb = pb < L ? lay[pb] : kDropped;
         }
         z.rule = y.rule;
         z.pa = pa;
