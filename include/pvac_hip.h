@@ -590,6 +590,64 @@ int pvac_hip_batch_sumdigest(pvac_hip_ctx* ctx, const pvac_ct_batch* X, uint64_t
  * counterpart: the reference's Ciphers are std::vectors of exact size (core/types.hpp:95-98). */
 int pvac_hip_batch_pack(pvac_hip_ctx* ctx, const pvac_ct_batch* src, pvac_ct_batch* dst, uint64_t* totals);
 
+/* ---------------------------------------------------------------- batch_gather
+ * Regroups whole ciphers of resident batches on the device: output cipher k of dst is a verbatim copy of
+ * cipher pick_idx[k] of srcs[pick_src[k]]: its l_cnt layer records (all 40 bytes, pad included), its e_cnt
+ * edge rows (meta, w_lo, w_hi) and, when dst->sigma is set, its sigma rows. Layer ids and PROD parents are
+ * cipher-relative, so nothing is rewritten. Concat, select, permute, repeat and split are all this call.
+ * Sources are dense or capacity-padded CSR with any offsets; slots past a cipher's counts are never read.
+ * dst comes out as dense CSR: l_cnt / e_cnt copied, l_off / e_off their exclusive scans, dst->n = m. A
+ * cipher may be picked any number of times and a source may go unused. No reference counterpart (its
+ * Ciphers are std::vectors a caller moves around at will).
+ * Null picks: pick_src == NULL with pick_idx given requires n_src == 1, and every pick comes from srcs[0];
+ * pick_idx == NULL requires pick_src == NULL and m == the sum of srcs[j].n: the output is the
+ * concatenation of the sources in order, and no pick list is built.
+ * Contract: dst's arrays overlap no source's (documented, not checked).
+ *
+ * pvac_hip_batch_gather_plan validates before anything is written to dst: PVAC_EINVAL for n_src == 0 with
+ * m > 0, n_src > PVAC_GATHER_MAX_SOURCES, the null-pick rules, dst->sigma set while any source has no
+ * sigma or a different sigma_words, and (found on the device, reported with the totals' read-back) a
+ * pick_src[k] >= n_src or a pick_idx[k] >= srcs[pick_src[k]].n; PVAC_ENOSYS for m >= 2^31 - 1. Otherwise it
+ * writes dst's four index arrays (m entries) and sets totals[0], [1] (HOST) to the layer and edge rows
+ * needed. It synchronises once. The uploaded source table and the tile tables live in storage of the
+ * gather's own, so a pending plan of another operation stays valid. dst's rows (and dst->sigma) are
+ * allocated between plan and exec; tiles are dealt for both a weights-only copy and one with the sources'
+ * common sigma width.
+ *
+ * pvac_hip_batch_gather_exec takes this context's latest gather plan only, for the same G (sources, picks,
+ * m) and the same index arrays of dst (PVAC_EINVAL otherwise; dst->sigma is checked as by the plan).
+ * PVAC_ENOMEM, with nothing written, when the plan's totals exceed layer_cap / edge_cap (the capacity
+ * check pvac_hip_batch_pack lacks). m == 0 launches nothing. Enqueued on the context's stream; not
+ * synchronous. Timing label "batch_gather". A plan may be executed more than once.
+ *
+ * Work is dealt in tiles numbered through the output: at most ept consecutive edge rows of one cipher
+ * (16 KiB of meta, w_lo, w_hi and sigma words) or at most lpt consecutive layer records of one, a wave per
+ * tile, four tiles in flight per workgroup, each wave taking a run of consecutive tiles, the grid capped
+ * at 8 workgroups per CU. One 345 K-edge cipher spreads over the device and 2^20 small ciphers do not
+ * cost a workgroup each. Edge arrays move 16 bytes per lane where a tile's source and destination
+ * addresses agree mod 16 after an 8-byte head (8-byte tail for an odd end), 8 bytes where they do not;
+ * sigma rows 16 bytes when sigma_words is even and dst's and every source's sigma base is 16-byte aligned,
+ * 8 bytes otherwise; layer records as 8-byte words. No store lands outside the rows of the cipher copied.
+ *
+ * pvac_hip_batch_gather_path_count, since the context was created: out[0] / out[1] = exec calls (m > 0)
+ * whose sigma rows moved 16 / 8 bytes at a time (a call without sigma counts under out[1], as in the
+ * codec), out[2] = tiles dealt, out[3] = output ciphers.
+ * pvac_hip_batch_gather_tile (host only, no context): out[0] = ept, out[1] = lpt for a sigma width
+ * (0 = weights only). */
+#define PVAC_GATHER_MAX_SOURCES 1024
+typedef struct pvac_gather {
+    const pvac_ct_batch* srcs;  /* HOST [n_src] descriptors of DEVICE arrays on the context's device */
+    uint32_t n_src, pad;
+    uint64_t m;                 /* output ciphers */
+    const uint32_t* pick_src;   /* DEVICE [m], nullable */
+    const uint64_t* pick_idx;   /* DEVICE [m], nullable */
+} pvac_gather;
+int pvac_hip_batch_gather_plan(pvac_hip_ctx* ctx, const pvac_gather* G, pvac_ct_batch* dst, uint64_t totals[2]);
+int pvac_hip_batch_gather_exec(pvac_hip_ctx* ctx, const pvac_gather* G, pvac_ct_batch* dst, uint64_t layer_cap,
+                               uint64_t edge_cap);
+int pvac_hip_batch_gather_path_count(pvac_hip_ctx* ctx, uint64_t out[4]);
+int pvac_hip_batch_gather_tile(uint32_t sigma_words, uint32_t out[2]);
+
 /* ---------------------------------------------------------------- LPN PRF
  * SecKey (core/types.hpp:134-137): prf_k and the LPN secret (ceil(lpn_n/64) words, host) with
  * pk.prm's lpn_t and noise rate tau_num/tau_den. The PRF also needs pk.H_digest: it is taken

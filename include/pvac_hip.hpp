@@ -1361,7 +1361,66 @@ public:
         return out;
     }
 
+    // ---- regrouping resident batches (pvac_hip_batch_gather_plan / _exec)
+    // Output cipher k = cipher pick_idx[k] of srcs[pick_src[k]], copied on the device into a batch that
+    // owns its arrays (as batch_from_image's result does). pick_src empty with pick_idx given: every
+    // pick comes from the one source. The sources must agree on sigma_bits (Error(PVAC_EINVAL)); the
+    // result carries it, sigma rows included. Two .ct files become one in a single step:
+    // batch_from_image twice, concat, ct_image.
+    device_batch gather(const std::vector<const device_batch*>& srcs, const std::vector<uint32_t>& pick_src,
+                        const std::vector<uint64_t>& pick_idx) {
+        if (!pick_src.empty() && pick_src.size() != pick_idx.size())
+            throw Error(PVAC_EINVAL, "gather: pick_src and pick_idx differ in length");
+        detail::dev_array<uint32_t> ps(pick_src.size());
+        detail::dev_array<uint64_t> pi(pick_idx.size());
+        ps.upload(pick_src.data(), pick_src.size(), stream_);
+        pi.upload(pick_idx.data(), pick_idx.size(), stream_);
+        // no picks at all is the empty batch, not the concatenation: both lists stay non-null
+        return gather_run(srcs, pick_idx.size(), pick_src.empty() && !pick_idx.empty() ? nullptr : ps.p, pi.p);
+    }
+
+    // the sources' ciphers in order
+    device_batch concat(const std::vector<const device_batch*>& srcs) {
+        uint64_t m = 0;
+        for (const device_batch* s : srcs) m += s ? s->arrays.l_cnt.size() : 0;
+        return gather_run(srcs, m, nullptr, nullptr);
+    }
+
 private:
+    device_batch gather_run(const std::vector<const device_batch*>& srcs, uint64_t m, const uint32_t* pick_src,
+                            const uint64_t* pick_idx) {
+        std::vector<pvac_ct_batch> views;
+        device_batch out;
+        for (const device_batch* s : srcs) {
+            if (!s) throw Error(PVAC_EINVAL, "gather: null source");
+            if (!views.empty() && s->sigma_bits != out.sigma_bits)
+                throw Error(PVAC_EINVAL, "gather: the sources disagree on sigma_bits");
+            out.sigma_bits = s->sigma_bits;
+            views.push_back(const_cast<device_batch*>(s)->view());
+        }
+        const bool sig = out.sigma_bits != 0;
+        const uint32_t sw = views.empty() ? 0 : views[0].sigma_words;
+        pvac_gather G{};
+        G.srcs = views.data();
+        G.n_src = (uint32_t)views.size();
+        G.m = m;
+        G.pick_src = pick_src;
+        G.pick_idx = pick_idx;
+        detail::batch& b = out.arrays;
+        b.d_l_off.alloc(m); b.d_l_cnt.alloc(m); b.d_e_off.alloc(m); b.d_e_cnt.alloc(m);
+        pvac_ct_batch v{};
+        v.l_off = b.d_l_off.p; v.l_cnt = b.d_l_cnt.p; v.e_off = b.d_e_off.p; v.e_cnt = b.d_e_cnt.p;
+        uint64_t tot[2] = {0, 0};
+        check(pvac_hip_batch_gather_plan(ctx_, &G, &v, tot));
+        detail::alloc_out(b, m, tot[0], tot[1], sw, sig);
+        v = b.view(sig);
+        v.n = m;
+        check(pvac_hip_batch_gather_exec(ctx_, &G, &v, tot[0], tot[1]));
+        // the pick lists and the views die with this call: the rows must have been read by then
+        detail::hip_ok(hipStreamSynchronize(stream_), "sync");
+        return out;
+    }
+
     void check(int rc) {
         if (rc) throw Error(rc, std::string("pvac_hip: ") + pvac_hip_last_error(ctx_));
     }

@@ -95,6 +95,15 @@ class Lincomb(C.Structure):
 
 TERM_SCALE = 0x1
 
+GATHER_MAX_SOURCES = 1024
+
+
+class Gather(C.Structure):
+    """pvac_gather: the sources (a host array of CtBatch) and pick lists (device pointers) of a batch_gather."""
+    _fields_ = [("srcs", C.c_void_p), ("n_src", C.c_uint32), ("pad", C.c_uint32), ("m", C.c_uint64),
+                ("pick_src", C.c_void_p), ("pick_idx", C.c_void_p)]
+
+
 FILL_NONCES_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p)
 ON_CHUNK_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(CtBatch), C.c_void_p)
 # pvac_chain_step_fn(user, step, first_input, A, X, C, dev_words, n_words, stream): nonces_at / after_step / salts_at
@@ -191,6 +200,10 @@ def load_library(path: str = _LIB_PATH) -> C.CDLL:
         "pvac_hip_layer_gsum": ([vp, C.POINTER(CtBatch), vp, vp], i32),
         "pvac_hip_metrics_path_count": ([vp, C.POINTER(u64)], i32),
         "pvac_hip_batch_pack": ([vp, C.POINTER(CtBatch), C.POINTER(CtBatch), C.POINTER(u64)], i32),
+        "pvac_hip_batch_gather_plan": ([vp, C.POINTER(Gather), C.POINTER(CtBatch), C.POINTER(u64)], i32),
+        "pvac_hip_batch_gather_exec": ([vp, C.POINTER(Gather), C.POINTER(CtBatch), u64, u64], i32),
+        "pvac_hip_batch_gather_path_count": ([vp, C.POINTER(u64)], i32),
+        "pvac_hip_batch_gather_tile": ([u32, C.POINTER(u32)], i32),
         "pvac_hip_bucket_count": ([u64], u64),
         "pvac_hip_chain_partition": ([u64, u64, u32, vp], i32),
         "pvac_hip_memcpy": ([vp, vp, C.c_size_t, vp], i32),
@@ -1112,6 +1125,76 @@ class Engine:
         nl, ne = int(tot[0]), int(tot[1])
         return DeviceBatch(X.n, D.l_off, D.l_cnt, D.layers[:nl], D.e_off, D.e_cnt, D.meta[:ne], D.w_lo[:ne],
                            D.w_hi[:ne], D.sigma[:ne] if sig else None)
+
+    # ---- regrouping resident batches (pvac_hip_batch_gather_plan / _exec)
+    def gather(self, sources, pick_src=None, pick_idx=None, sigma=None) -> DeviceBatch:
+        """Output cipher k = a verbatim copy of cipher pick_idx[k] of sources[pick_src[k]], as a dense batch
+        whose arrays are exactly the planned size. pick_src=None takes every pick from the one source;
+        pick_idx=None (then pick_src is None too) concatenates the sources in order. Picks may be numpy
+        arrays, lists or CUDA tensors. sigma=None carries the sigma rows iff every source has them;
+        sigma=True insists (PvacError otherwise), sigma=False copies none."""
+        torch = self.torch
+        sources = list(sources)
+        if pick_idx is None and pick_src is not None:
+            raise PvacError("gather: pick_src needs pick_idx")
+        have = bool(sources) and all(s.sigma is not None for s in sources)
+        if sigma is None:
+            sigma = have and len({s.sigma.shape[1] for s in sources}) == 1
+        widths = {s.sigma.shape[1] for s in sources} if have else set()
+        if sigma and len(widths) != 1:
+            raise PvacError("gather: sigma=True needs sigma rows of one width on every source")
+        sw = widths.pop() if sigma else 0
+        structs = (CtBatch * max(len(sources), 1))(*[s.struct() for s in sources])
+        if pick_idx is None:
+            m = sum(s.n for s in sources)
+            ps = pi = None
+        else:
+            m = len(pick_idx)
+            pi = self._index_tensor(pick_idx)
+            ps = None if pick_src is None else self._index_tensor(pick_src, np.uint32)
+            if ps is not None and len(pick_src) != m:
+                raise PvacError("gather: pick_src and pick_idx differ in length")
+        G = Gather(C.cast(structs, C.c_void_p), len(sources), 0, m, None if ps is None else ps.data_ptr(),
+                   None if pi is None else pi.data_ptr())
+        z = lambda: torch.zeros(max(m, 1), dtype=torch.int64, device=self.device)
+        D = DeviceBatch(m, z(), z(), None, z(), z(), None, None, None)
+        tot = (C.c_uint64 * 2)()
+        sd = D.struct()
+        self._check(self.lib.pvac_hip_batch_gather_plan(self.ctx, C.byref(G), C.byref(sd), tot))
+        nl, ne = int(tot[0]), int(tot[1])
+        rows = lambda k, *w: torch.empty((max(k, 1),) + w, dtype=torch.int64, device=self.device)[:k]
+        D.layers, D.meta, D.w_lo, D.w_hi = rows(nl, 5), rows(ne), rows(ne), rows(ne)
+        if sigma:
+            D.sigma = rows(ne, sw)
+        sd = D.struct()
+        self._check(self.lib.pvac_hip_batch_gather_exec(self.ctx, C.byref(G), C.byref(sd), nl, ne))
+        return D
+
+    def cat(self, batches, sigma=None) -> DeviceBatch:
+        """The ciphers of `batches` in order as one dense batch (gather without picks)."""
+        return self.gather(batches, sigma=sigma)
+
+    def select(self, X: DeviceBatch, idx, sigma=None) -> DeviceBatch:
+        """Ciphers idx[0], idx[1], ... of X (any order, repeats allowed) as a dense batch."""
+        return self.gather([X], None, idx, sigma=sigma)
+
+    def split(self, X: DeviceBatch, sizes):
+        """X cut into consecutive dense batches of sizes[0], sizes[1], ... ciphers (their sum is X.n)."""
+        sizes = [int(s) for s in sizes]
+        if sum(sizes) != X.n or min(sizes, default=0) < 0:
+            raise PvacError("split: sizes must be non-negative and sum to the batch's ciphers")
+        out, at = [], 0
+        for s in sizes:
+            out.append(self.select(X, np.arange(at, at + s, dtype=np.uint64)))
+            at += s
+        return out
+
+    def gather_path_counts(self):
+        """Since the context was created: gather execs on the 16-byte / 8-byte sigma path, tiles dealt and
+        output ciphers."""
+        v = (C.c_uint64 * 4)()
+        self._check(self.lib.pvac_hip_batch_gather_path_count(self.ctx, v))
+        return {"wide": int(v[0]), "narrow": int(v[1]), "tiles": int(v[2]), "ciphers": int(v[3])}
 
     # ---- the device .ct codec
     def ct_image(self, batch: DeviceBatch, sigma_bits=8192, return_pos=False):

@@ -5,6 +5,7 @@
 
 #include "../../include/pvac_hip.h"
 #include "fp127.hpp"
+#include "gather_tiles.hpp"
 
 namespace pvhip {
 
@@ -603,5 +604,38 @@ hipError_t launch_ct_image_write(const pvac_ct_batch& X, uint32_t nbits, const u
 hipError_t launch_ct_image_parse(const uint8_t* image, uint64_t len, const uint64_t* pos, uint64_t n, uint32_t nbits,
                                  const pvac_ct_batch& X, uint64_t layer_cap, uint64_t edge_cap, uint32_t* status, uint64_t* words,
                                  uint64_t* scan_scratch, unsigned long long* ctl, bool wide, int num_cus, hipStream_t st);
+
+// ---- batch_gather (k_gather.hip, gather_tiles.hpp): whole ciphers of several resident batches into one dense batch
+// ctl: 0 / 1 = layer and edge totals, 2 = tiles of a weights-only copy, 3 = picks out of range, 4 = tiles with sigma
+constexpr int kGatherCtlWords = 5;
+// The plan's own arrays, m entries each: the picked ciphers' counts (cL, cE), their dense offsets in the
+// output (oL, oE: the scans of the counts), the scans of the tile counts of a weights-only copy (toff,
+// geometry g) and of a copy with sigma rows (toff_s, geometry gs; null when the sources cannot give sigma:
+// dst's rows, sigma included, are allocated between plan and exec, so the plan deals for both), the
+// source's row offsets (sL, sE) and the source index (src).
+struct gather_plan_args {
+    const pvac_ct_batch* srcs;   // DEVICE table of the n_src source descriptors
+    const uint64_t* first;       // DEVICE, n_src + 1: first output of source j in a concatenation
+    uint32_t n_src;
+    gather_geom g, gs;
+    uint64_t m;
+    const uint32_t* pick_src;    // nullable
+    const uint64_t* pick_idx;    // null: concatenation
+    uint64_t *cL, *cE, *oL, *oE, *toff, *toff_s, *sL, *sE;
+    uint32_t* src;
+    unsigned long long* ctl;
+};
+struct gather_exec_args {
+    const pvac_ct_batch* srcs;
+    pvac_ct_batch dst;           // row arrays (sigma null: no sigma rows are copied)
+    const uint64_t *cL, *cE, *oL, *oE, *toff, *sL, *sE;   // toff: the table of g's geometry
+    const uint32_t* src;
+    uint64_t m, ntiles;
+    gather_geom g;
+};
+// the pick pass, the scans and, when every pick is in range, dst's four index arrays; nothing is read back here
+hipError_t launch_gather_plan(const gather_plan_args& a, const pvac_ct_batch& dst, uint64_t* scan_scratch, hipStream_t st);
+// the rows of every tile; wide: sigma rows by 16-byte pieces (gather_sigma_wide)
+hipError_t launch_gather_rows(const gather_exec_args& a, bool wide, int num_cus, hipStream_t st);
 
 }  // namespace pvhip

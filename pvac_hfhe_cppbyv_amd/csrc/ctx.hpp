@@ -239,6 +239,22 @@ struct pvac_hip_ctx {
         uint32_t plan_nbits = 0, plan_tile_edges = 0;
         uint64_t path[4] = {};                      // writes wide / 8-byte sigma path, parses wide / 8-byte
     } codec;
+    struct {   // pvac_hip_batch_gather (rt_gather.cpp, k_gather.hip): storage of its own, so no other plan goes stale
+        pvhip::dev_buf<uint64_t> words;             // the latest plan's eight per-output arrays (gather_plan_args)
+        pvhip::dev_buf<uint32_t> src;               // ... and the source of every output cipher
+        pvhip::dev_buf<uint64_t> table;             // the uploaded source descriptors, then their first outputs
+        pvhip::dev_buf<unsigned long long> ctl;     // kGatherCtlWords
+        std::vector<pvac_ct_batch> srcs;            // the latest plan (planned: there is one): its sources,
+        std::vector<uint64_t> first;                // their first outputs in a concatenation,
+        bool planned = false;
+        uint64_t m = 0, total_layers = 0, total_edges = 0;   // its shape and totals,
+        uint64_t tiles = 0, tiles_sigma = 0;        // its tiles without and with sigma rows of
+        uint32_t sigma_words = 0;                   // the sources' common width (0: they cannot give sigma),
+        const uint32_t* pick_src = nullptr;         // its pick lists
+        const uint64_t* pick_idx = nullptr;
+        const uint64_t* dst_index[4] = {};          // and dst's l_off, l_cnt, e_off, e_cnt
+        uint64_t path[4] = {};                      // execs wide / 8-byte sigma path, tiles dealt, output ciphers
+    } gather;
     struct {
         bool on = false;
         std::map<std::string, pvhip::timer_rec> timers;
