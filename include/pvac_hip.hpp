@@ -191,6 +191,9 @@ struct pinned_alloc : default_init<T> {
     bool operator!=(const pinned_alloc<U>&) const noexcept { return false; }
 };
 
+// What an array of a batch has one element per (sigma: sigma_words per edge).
+enum class rows { cipher, layer, edge, sigma };
+
 // Host SoA image of a batch of reference Ciphers + its device copy.
 template <bool Pinned>
 struct basic_batch {
@@ -202,25 +205,70 @@ struct basic_batch {
     dev_array<pvac_layer> d_layers;
     uint32_t sigma_words = 0;
 
-    // frees every host and device array (an engine-owned batch between calls)
-    void release() {
-        basic_batch e;
-        std::swap(l_off, e.l_off); std::swap(l_cnt, e.l_cnt); std::swap(e_off, e.e_off); std::swap(e_cnt, e.e_cnt);
-        std::swap(meta, e.meta); std::swap(w_lo, e.w_lo); std::swap(w_hi, e.w_hi); std::swap(sigma, e.sigma);
-        std::swap(layers, e.layers);
-        for (auto* d : {&d_l_off, &d_l_cnt, &d_e_off, &d_e_cnt, &d_meta, &d_w_lo, &d_w_hi, &d_sigma}) d->release();
-        d_layers.release();
+    // The nine arrays, stated once: f(host array, device array, the pvac_ct_batch field the device
+    // array is seen through, what it has one element per), in the order copies are issued. Release,
+    // the views, upload and download below all come from this list.
+    template <class F>
+    void each(F f) {
+        f(l_off, d_l_off, &pvac_ct_batch::l_off, rows::cipher);
+        f(l_cnt, d_l_cnt, &pvac_ct_batch::l_cnt, rows::cipher);
+        f(e_off, d_e_off, &pvac_ct_batch::e_off, rows::cipher);
+        f(e_cnt, d_e_cnt, &pvac_ct_batch::e_cnt, rows::cipher);
+        f(layers, d_layers, &pvac_ct_batch::layers, rows::layer);
+        f(meta, d_meta, &pvac_ct_batch::meta, rows::edge);
+        f(w_lo, d_w_lo, &pvac_ct_batch::w_lo, rows::edge);
+        f(w_hi, d_w_hi, &pvac_ct_batch::w_hi, rows::edge);
+        f(sigma, d_sigma, &pvac_ct_batch::sigma, rows::sigma);
     }
 
-    pvac_ct_batch view(bool with_sigma) {
+    // frees every host and device array (an engine-owned batch between calls)
+    void release() {
+        each([](auto& h, auto& d, auto, rows) {
+            typename std::decay<decltype(h)>::type().swap(h);
+            d.release();
+        });
+    }
+
+    // n ciphers over the device arrays: the per-cipher arrays always, the others with the rows, sigma
+    // only when asked for as well
+    pvac_ct_batch view_of(uint64_t n, bool with_rows, bool with_sigma, uint32_t words) {
         pvac_ct_batch b{};
-        b.n = l_cnt.size();
-        b.l_off = d_l_off.p; b.l_cnt = d_l_cnt.p; b.layers = d_layers.p;
-        b.e_off = d_e_off.p; b.e_cnt = d_e_cnt.p;
-        b.meta = d_meta.p; b.w_lo = d_w_lo.p; b.w_hi = d_w_hi.p;
-        b.sigma = with_sigma ? d_sigma.p : nullptr;
-        b.sigma_words = sigma_words;
+        b.n = n;
+        b.sigma_words = words;
+        each([&](auto&, auto& d, auto field, rows r) {
+            if (r == rows::cipher || (with_rows && (r != rows::sigma || with_sigma))) b.*field = d.p;
+        });
         return b;
+    }
+    pvac_ct_batch view(bool with_sigma) { return view_of(l_cnt.size(), true, with_sigma, sigma_words); }
+
+    // An output batch of n ciphers in the order a plan / exec pair fills it. Before the plan: the
+    // per-cipher arrays and the view a plan takes, with nothing else set (words: ct_lincomb's plan
+    // reads sigma_words, the others leave 0).
+    void alloc_index(size_t n) { d_l_off.alloc(n); d_l_cnt.alloc(n); d_e_off.alloc(n); d_e_cnt.alloc(n); }
+    pvac_ct_batch plan_view(uint32_t words = 0) { return view_of(0, false, false, words); }
+    // After it: rows of capacity layer / edge slots (the per-cipher arrays, whose offsets the plan
+    // wrote, are kept) and the view exec writes.
+    void alloc_rows(size_t n, uint64_t lslots, uint64_t eslots, uint32_t words, bool with_sigma) {
+        sigma_words = words;
+        const uint64_t count[] = {n, lslots, eslots, eslots * words};
+        each([&](auto&, auto& d, auto, rows r) {
+            if (r != rows::cipher && (r != rows::sigma || with_sigma)) d.alloc(count[(int)r]);
+        });
+        l_cnt.resize(n);
+    }
+    pvac_ct_batch out_view(uint64_t n, bool with_sigma) { return view_of(n, true, with_sigma, sigma_words); }
+
+    // host arrays <- the device arrays of v, asynchronously: the per-cipher arrays of its n ciphers
+    // (index) or its rows, sigma when v has it
+    void fetch(const pvac_ct_batch& v, bool index, uint64_t n, uint64_t lslots, uint64_t eslots, hipStream_t s) {
+        sigma_words = v.sigma_words;
+        const uint64_t count[] = {n, lslots, eslots, eslots * sigma_words};
+        each([&](auto& h, auto&, auto field, rows r) {
+            if ((r == rows::cipher) != index || (r == rows::sigma && !v.sigma)) return;
+            h.resize(count[(int)r]);
+            if (!h.empty()) hip_ok(hipMemcpyAsync(h.data(), v.*field, h.size() * sizeof h[0], hipMemcpyDeviceToHost, s), "D2H");
+        });
     }
 };
 using batch = basic_batch<false>;
@@ -279,26 +327,11 @@ void to_host(const std::vector<const CipherT*>& cs, uint32_t sigma_words, bool w
 
 template <class Batch>
 void upload(Batch& b, hipStream_t s, bool with_sigma) {
-    b.d_l_off.alloc(b.l_off.size()); b.d_l_off.upload(b.l_off.data(), b.l_off.size(), s);
-    b.d_l_cnt.alloc(b.l_cnt.size()); b.d_l_cnt.upload(b.l_cnt.data(), b.l_cnt.size(), s);
-    b.d_e_off.alloc(b.e_off.size()); b.d_e_off.upload(b.e_off.data(), b.e_off.size(), s);
-    b.d_e_cnt.alloc(b.e_cnt.size()); b.d_e_cnt.upload(b.e_cnt.data(), b.e_cnt.size(), s);
-    b.d_layers.alloc(b.layers.size()); b.d_layers.upload(b.layers.data(), b.layers.size(), s);
-    b.d_meta.alloc(b.meta.size()); b.d_meta.upload(b.meta.data(), b.meta.size(), s);
-    b.d_w_lo.alloc(b.w_lo.size()); b.d_w_lo.upload(b.w_lo.data(), b.w_lo.size(), s);
-    b.d_w_hi.alloc(b.w_hi.size()); b.d_w_hi.upload(b.w_hi.data(), b.w_hi.size(), s);
-    if (with_sigma) { b.d_sigma.alloc(b.sigma.size()); b.d_sigma.upload(b.sigma.data(), b.sigma.size(), s); }
-}
-
-// Output records of capacity layer/edge slots; the per-cipher offset/count arrays were
-// allocated before the plan (which writes the offsets) and are kept.
-template <class Batch>
-void alloc_out(Batch& c, size_t n, uint64_t lslots, uint64_t eslots, uint32_t sigma_words, bool with_sigma) {
-    c.sigma_words = sigma_words;
-    c.d_layers.alloc(lslots);
-    c.d_meta.alloc(eslots); c.d_w_lo.alloc(eslots); c.d_w_hi.alloc(eslots);
-    if (with_sigma) c.d_sigma.alloc(eslots * sigma_words);
-    c.l_cnt.resize(n);
+    b.each([&](auto& h, auto& d, auto, rows r) {
+        if (r == rows::sigma && !with_sigma) return;
+        d.alloc(h.size());
+        d.upload(h.data(), h.size(), s);
+    });
 }
 
 // host SoA image (c.l_off ... c.sigma filled) -> reference Ciphers
@@ -336,63 +369,47 @@ std::vector<CipherT> convert_host(Batch& c, size_t n, uint32_t m_bits, bool with
     return out;
 }
 
-// device records of d (lslots / eslots rows) -> host SoA image c, synchronous
-template <class Batch, class Dev>
-void download(Batch& c, const Dev& d, size_t n, uint64_t lslots, uint64_t eslots, bool with_sigma, hipStream_t s) {
-    c.sigma_words = d.sigma_words;
-    c.l_off.resize(n); c.l_cnt.resize(n); c.e_off.resize(n); c.e_cnt.resize(n);
-    c.layers.resize(lslots); c.meta.resize(eslots); c.w_lo.resize(eslots); c.w_hi.resize(eslots);
-    d.d_l_off.download(c.l_off.data(), n, s); d.d_l_cnt.download(c.l_cnt.data(), n, s);
-    d.d_e_off.download(c.e_off.data(), n, s); d.d_e_cnt.download(c.e_cnt.data(), n, s);
-    d.d_layers.download(c.layers.data(), lslots, s);
-    d.d_meta.download(c.meta.data(), eslots, s);
-    d.d_w_lo.download(c.w_lo.data(), eslots, s); d.d_w_hi.download(c.w_hi.data(), eslots, s);
-    if (with_sigma) {
-        c.sigma.resize(eslots * c.sigma_words);
-        d.d_sigma.download(c.sigma.data(), c.sigma.size(), s);
-    }
+// device records of the view v (n ciphers; lslots / eslots rows) -> host SoA image c, synchronous
+template <class Batch>
+void download(Batch& c, const pvac_ct_batch& v, size_t n, uint64_t lslots, uint64_t eslots, hipStream_t s) {
+    c.fetch(v, true, n, lslots, eslots, s);
+    c.fetch(v, false, n, lslots, eslots, s);
     hip_ok(hipStreamSynchronize(s), "sync");
 }
 
 template <class CipherT>
 std::vector<CipherT> from_device(batch& c, size_t n, uint64_t lslots, uint64_t eslots, uint32_t m_bits,
                                  bool with_sigma, hipStream_t s) {
-    download(c, c, n, lslots, eslots, with_sigma, s);
+    download(c, c.out_view(n, with_sigma), n, lslots, eslots, s);
     return convert_host<CipherT>(c, n, m_bits, with_sigma);
 }
 
-// small synchronous device -> host copies of a batch view handed to a chain hook (valid only there)
-inline hvec<uint64_t> d2h_u64(const uint64_t* p, size_t n, hipStream_t s) {
-    hvec<uint64_t> v(n);
-    if (n) hip_ok(hipMemcpyAsync(v.data(), p, n * 8, hipMemcpyDeviceToHost, s), "D2H");
+// a small device array -> host, synchronous (a status or digest array; an array of a batch view
+// handed to a chain hook, valid only there)
+template <class T>
+hvec<T> d2h(const T* p, size_t n, hipStream_t s) {
+    hvec<T> v(n);
+    if (n) hip_ok(hipMemcpyAsync(v.data(), p, n * sizeof(T), hipMemcpyDeviceToHost, s), "D2H");
     hip_ok(hipStreamSynchronize(s), "sync");
     return v;
 }
 
-// the used rows of a capacity-padded device batch view -> reference Ciphers
+// the used rows of a capacity-padded device batch view -> reference Ciphers: the per-cipher arrays
+// first, which say how many rows there are
 template <class CipherT>
 std::vector<CipherT> from_view(const pvac_ct_batch& v, uint32_t m_bits, hipStream_t s) {
     batch c;
     const size_t n = v.n;
-    c.l_off = d2h_u64(v.l_off, n, s); c.l_cnt = d2h_u64(v.l_cnt, n, s);
-    c.e_off = d2h_u64(v.e_off, n, s); c.e_cnt = d2h_u64(v.e_cnt, n, s);
+    c.fetch(v, true, n, 0, 0, s);
+    hip_ok(hipStreamSynchronize(s), "sync");
     uint64_t nl = 0, ne = 0;
     for (size_t i = 0; i < n; ++i) {
         nl = std::max(nl, c.l_off[i] + c.l_cnt[i]);
         ne = std::max(ne, c.e_off[i] + c.e_cnt[i]);
     }
-    const bool sig = v.sigma != nullptr;
-    c.sigma_words = v.sigma_words;
-    c.layers.resize(nl); c.meta.resize(ne); c.w_lo.resize(ne); c.w_hi.resize(ne);
-    if (sig) c.sigma.resize(ne * c.sigma_words);
-    auto get = [&](void* dst, const void* src, size_t bytes) {
-        if (bytes) hip_ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s), "D2H");
-    };
-    get(c.layers.data(), v.layers, nl * sizeof(pvac_layer));
-    get(c.meta.data(), v.meta, ne * 8); get(c.w_lo.data(), v.w_lo, ne * 8); get(c.w_hi.data(), v.w_hi, ne * 8);
-    if (sig) get(c.sigma.data(), v.sigma, c.sigma.size() * 8);
+    c.fetch(v, false, n, nl, ne, s);
     hip_ok(hipStreamSynchronize(s), "sync");
-    return convert_host<CipherT>(c, n, m_bits, sig);
+    return convert_host<CipherT>(c, n, m_bits, v.sigma != nullptr);
 }
 
 // The ragged term lists of a ct_lincomb call as the C ABI takes them (pvac_lincomb, host side):
@@ -453,8 +470,7 @@ public:
     Engine& operator=(const Engine&) = delete;
     ~Engine() {
         if (stream_) (void)hipStreamSynchronize(stream_);
-        mul_a_.release(); mul_b_.release(); mul_c_.release(); mul_p_.release();
-        mul_nonces_.release(); mul_salts_.release(); mul_status_.release();
+        release_mul();
         pvac_hip_ctx_destroy(ctx_);
     }
 
@@ -491,8 +507,7 @@ public:
     // batch so far; trim() hands them back.
     void trim() {
         detail::hip_ok(hipStreamSynchronize(stream_), "sync");
-        mul_a_.release(); mul_b_.release(); mul_c_.release(); mul_p_.release();
-        mul_nonces_.release(); mul_salts_.release(); mul_status_.release();
+        release_mul();
     }
 
     // H regenerated on the device from canon_tag (gen_H, crypto/matrix.hpp:191-251); returns the
@@ -548,9 +563,8 @@ public:
         detail::hip_ok(hipStreamSynchronize(stream_), "sync");
         lap(phases_.h2d);
         pvac_ct_batch va = a.view(false), vb = b.view(false);
-        c.d_l_off.alloc(n); c.d_l_cnt.alloc(n); c.d_e_off.alloc(n); c.d_e_cnt.alloc(n);
-        pvac_ct_batch vc{};
-        vc.l_off = c.d_l_off.p; vc.l_cnt = c.d_l_cnt.p; vc.e_off = c.d_e_off.p; vc.e_cnt = c.d_e_cnt.p;
+        c.alloc_index(n);
+        pvac_ct_batch vc = c.plan_view();
         pvac_hip_plan plan{};
         check(pvac_hip_ct_mul_plan(ctx_, &va, &vb, &vc, &plan));
         // nonces per pair in the reference's draw order: (la, lb) row-major, lo then hi
@@ -569,10 +583,9 @@ public:
         detail::dev_array<uint64_t>& d_nonces = mul_nonces_;
         d_nonces.alloc(nonces.size());
         d_nonces.upload(nonces.data(), nonces.size(), stream_);
-        detail::alloc_out(c, n, plan.total_layer_slots, plan.total_edge_slots, sigma_words(), with_sigma);
+        c.alloc_rows(n, plan.total_layer_slots, plan.total_edge_slots, sigma_words(), with_sigma);
         lap(phases_.plan);
-        vc = c.view(false);
-        vc.n = n;
+        vc = c.out_view(n, false);
         check(pvac_hip_ct_mul_exec(ctx_, &plan, &va, &vb, d_nonces.p, nullptr, &vc, 0));
         if (with_sigma) {
             // one salt per emitted edge, drawn after the weights are known (arithmetic.hpp:90-94), in
@@ -598,29 +611,26 @@ public:
             detail::dev_array<uint64_t>& d_salts = mul_salts_;
             d_salts.alloc(salts.size());
             d_salts.upload(salts.data(), salts.size(), stream_);
-            vc = c.view(true);
-            vc.n = n;
+            vc = c.out_view(n, true);
             if (hash_order) {
                 check(pvac_hip_sigma_batch(ctx_, &vc, d_salts.p));
             } else {
                 check(pvac_hip_ct_mul_plan(ctx_, &va, &vb, &vc, &plan));
-                vc = c.view(true);
-                vc.n = n;
+                vc = c.out_view(n, true);
                 check(pvac_hip_ct_mul_exec(ctx_, &plan, &va, &vb, d_nonces.p, d_salts.p, &vc, PVAC_MUL_WITH_SIGMA));
             }
         }
         // only the used rows cross the link: packed on the device first (each pair's output kept its
         // plan capacity), then copied at their exact totals
         detail::pinned_batch& p = mul_p_;
-        p.d_l_off.alloc(n); p.d_l_cnt.alloc(n); p.d_e_off.alloc(n); p.d_e_cnt.alloc(n);
-        detail::alloc_out(p, n, plan.total_layer_slots, plan.total_edge_slots, sigma_words(), with_sigma);
-        vc = c.view(with_sigma);
-        vc.n = n;
-        pvac_ct_batch vp = p.view(with_sigma);
+        p.alloc_index(n);
+        p.alloc_rows(n, plan.total_layer_slots, plan.total_edge_slots, sigma_words(), with_sigma);
+        vc = c.out_view(n, with_sigma);
+        pvac_ct_batch vp = p.out_view(n, with_sigma);
         uint64_t tot[2] = {0, 0};
         check(pvac_hip_batch_pack(ctx_, &vc, &vp, tot));
         lap(phases_.exec);
-        detail::download(c, p, n, tot[0], tot[1], with_sigma, stream_);
+        detail::download(c, vp, n, tot[0], tot[1], stream_);
         lap(phases_.d2h);
         std::vector<CipherT> out = detail::convert_host<CipherT>(c, n, prm_.m_bits, with_sigma);
         lap(phases_.to_aos);
@@ -654,15 +664,10 @@ public:
         if (!n) return {};
         if (with_sigma) ensure_H(pk);
         detail::batch x;
-        detail::to_host(xs, sigma_words(), false, x);
-        detail::upload(x, stream_, false);
+        pvac_ct_batch vx = stage(xs, false, x);
         std::vector<detail::batch> yb(ops.size());
         std::vector<pvac_ct_batch> yv(ops.size());
-        for (size_t d = 0; d < ops.size(); ++d) {
-            detail::to_host(ops[d], sigma_words(), false, yb[d]);
-            detail::upload(yb[d], stream_, false);
-            yv[d] = yb[d].view(false);
-        }
+        for (size_t d = 0; d < ops.size(); ++d) yv[d] = stage(ops[d], false, yb[d]);
         detail::hip_ok(hipStreamSynchronize(stream_), "sync");
         struct state {
             std::vector<RandomSource>* rnds;
@@ -686,8 +691,8 @@ public:
             try {
                 state& S = *(state*)u;
                 const hipStream_t s = (hipStream_t)st;
-                const auto la = detail::d2h_u64(A->l_cnt, A->n, s), lx = detail::d2h_u64(X->l_cnt, X->n, s);
-                const auto lo = detail::d2h_u64(C->l_off, C->n, s);
+                const auto la = detail::d2h(A->l_cnt, A->n, s), lx = detail::d2h(X->l_cnt, X->n, s);
+                const auto lo = detail::d2h(C->l_off, C->n, s);
                 std::vector<uint64_t> w(nw, 0);
                 for (size_t i = 0; i < A->n; ++i) {
                     RandomSource& r = (*S.rnds)[c0 + i];
@@ -709,7 +714,7 @@ public:
             try {
                 state& S = *(state*)u;
                 if (S.sigma && step + 1 == S.depth) return 0;   // salts_at draws these
-                const auto ec = detail::d2h_u64(C->e_cnt, C->n, (hipStream_t)st);
+                const auto ec = detail::d2h(C->e_cnt, C->n, (hipStream_t)st);
                 for (size_t i = 0; i < C->n; ++i)
                     for (uint64_t k = 0; k < ec[i]; ++k) (void)(*S.rnds)[c0 + i]();
                 return 0;
@@ -722,7 +727,7 @@ public:
             try {
                 state& S = *(state*)u;
                 const hipStream_t s = (hipStream_t)st;
-                const auto ec = detail::d2h_u64(C->e_cnt, C->n, s), eo = detail::d2h_u64(C->e_off, C->n, s);
+                const auto ec = detail::d2h(C->e_cnt, C->n, s), eo = detail::d2h(C->e_off, C->n, s);
                 std::vector<uint64_t> w(nw ? nw : 1, 0);
                 for (size_t i = 0; i < C->n; ++i)
                     for (uint64_t k = 0; k < ec[i]; ++k) w[eo[i] + k] = (*S.rnds)[c0 + i]();
@@ -743,7 +748,6 @@ public:
                 return 1;
             }
         };
-        pvac_ct_batch vx = x.view(false);
         pvac_chain_stats st{};
         check(pvac_hip_ct_mul_chain(ctx_, &vx, &o, &st));
         return std::move(stt.out);
@@ -756,19 +760,11 @@ public:
         const size_t n = A.size();
         if (!n) return {};
         detail::batch a, b, c;
-        detail::to_host(A, sigma_words(), true, a);
-        detail::to_host(B, sigma_words(), true, b);
-        detail::upload(a, stream_, true);
-        detail::upload(b, stream_, true);
-        pvac_ct_batch va = a.view(true), vb = b.view(true);
-        c.d_l_off.alloc(n); c.d_l_cnt.alloc(n); c.d_e_off.alloc(n); c.d_e_cnt.alloc(n);
-        pvac_ct_batch vc{};
-        vc.l_off = c.d_l_off.p; vc.l_cnt = c.d_l_cnt.p; vc.e_off = c.d_e_off.p; vc.e_cnt = c.d_e_cnt.p;
+        pvac_ct_batch va = stage(A, true, a), vb = stage(B, true, b);
+        pvac_ct_batch vc = plan_out(c, n);
         pvac_hip_plan plan{};
         check(pvac_hip_ct_add_plan(ctx_, &va, &vb, &vc, &plan));
-        detail::alloc_out(c, n, plan.total_layer_slots, plan.total_edge_slots, sigma_words(), true);
-        vc = c.view(true);
-        vc.n = n;
+        vc = exec_out(c, n, plan.total_layer_slots, plan.total_edge_slots, sigma_words(), true);
         check(pvac_hip_ct_add_exec(ctx_, &plan, &va, &vb, negate_b ? 1 : 0, &vc));
         return detail::from_device<CipherT>(c, n, plan.total_layer_slots, plan.total_edge_slots, prm_.m_bits, true,
                                             stream_);
@@ -782,8 +778,7 @@ public:
         const size_t n = S.seg_off.size() - 1;
         if (!n) return {};
         detail::batch x, c;
-        detail::to_host(X, sigma_words(), with_sigma, x);
-        detail::upload(x, stream_, with_sigma);
+        const pvac_ct_batch vx = stage(X, with_sigma, x);
         detail::dev_array<uint64_t> d_so(S.seg_off.size()), d_tm(S.term.size()), d_sc(S.scale.size());
         detail::dev_array<uint32_t> d_fl(S.flags.size());
         d_so.upload(S.seg_off.data(), S.seg_off.size(), stream_);
@@ -797,16 +792,10 @@ public:
         s.term = d_tm.p;
         s.scale = S.scale.empty() ? nullptr : d_sc.p;
         s.flags = S.flags.empty() ? nullptr : d_fl.p;
-        const pvac_ct_batch vx = x.view(with_sigma);
-        c.d_l_off.alloc(n); c.d_l_cnt.alloc(n); c.d_e_off.alloc(n); c.d_e_cnt.alloc(n);
-        pvac_ct_batch vc{};
-        vc.l_off = c.d_l_off.p; vc.l_cnt = c.d_l_cnt.p; vc.e_off = c.d_e_off.p; vc.e_cnt = c.d_e_cnt.p;
-        vc.sigma_words = sigma_words();
+        pvac_ct_batch vc = plan_out(c, n, sigma_words());
         pvac_hip_plan plan{};
         check(pvac_hip_ct_lincomb_plan(ctx_, &vx, &s, &vc, &plan));
-        detail::alloc_out(c, n, plan.total_layer_slots, plan.total_edge_slots, sigma_words(), with_sigma);
-        vc = c.view(with_sigma);
-        vc.n = n;
+        vc = exec_out(c, n, plan.total_layer_slots, plan.total_edge_slots, sigma_words(), with_sigma);
         check(pvac_hip_ct_lincomb_exec(ctx_, &plan, &vx, &s, &vc));
         return detail::from_device<CipherT>(c, n, plan.total_layer_slots, plan.total_edge_slots, prm_.m_bits, with_sigma,
                                             stream_);
@@ -831,16 +820,12 @@ public:
     // under the same canon_tag replaces the device copy.
     template <class PubKeyT, class SecKeyT>
     void ensure_keys(const PubKeyT& pk, const SecKeyT& sk) {
-        // plan_noise's Params fields (core/types.hpp:48-50), read on every call like the reference
-        check(pvac_hip_ctx_set_noise(ctx_, (double)pk.prm.noise_entropy_bits, (double)pk.prm.tuple2_fraction,
-                                     (double)pk.prm.depth_slope_bits));
+        set_noise(pk);
         const std::vector<uint64_t> fp = key_fingerprint(sk);
         if (keys_ready_ && fp == key_fp_) return;
         if (!keys_ready_) {
             check(pvac_hip_ctx_set_H_digest(ctx_, pk.H_digest.data()));
-            std::vector<uint64_t> pg(2 * pk.powg_B.size());
-            for (size_t i = 0; i < pk.powg_B.size(); ++i) { pg[2 * i] = pk.powg_B[i].lo; pg[2 * i + 1] = pk.powg_B[i].hi; }
-            check(pvac_hip_ctx_set_powg(ctx_, pg.data(), (uint32_t)pk.powg_B.size()));
+            set_powg(pk);
         }
         check(pvac_hip_ctx_set_secret(ctx_, sk.prf_k.data(), sk.lpn_s_bits.data(), (uint32_t)pk.prm.lpn_n,
                                       (uint32_t)pk.prm.lpn_t, (uint32_t)pk.prm.lpn_tau_num,
@@ -913,11 +898,8 @@ public:
     // words of rnd each item of enc_items takes (for a caller that replays a recorded stream)
     template <class PubKeyT>
     std::vector<uint64_t> enc_items_draws(const PubKeyT& pk, const std::vector<EncItem>& its) {
-        check(pvac_hip_ctx_set_noise(ctx_, (double)pk.prm.noise_entropy_bits, (double)pk.prm.tuple2_fraction,
-                                     (double)pk.prm.depth_slope_bits));
-        std::vector<pvac_enc_item> items(its.size());
-        for (size_t i = 0; i < its.size(); ++i)
-            items[i] = pvac_enc_item{its[i].v_lo, its[i].v_hi, its[i].depth_hint, its[i].kind, 0, 0};
+        set_noise(pk);
+        const std::vector<pvac_enc_item> items = abi_items(its);
         std::vector<uint64_t> hint(its.size());
         check(pvac_hip_enc_items_caps(ctx_, items.size(), items.data(), nullptr, nullptr, hint.data()));
         return hint;
@@ -930,8 +912,7 @@ public:
         if (!n) return {};
         ensure_keys(pk, sk);
         if (with_sigma) ensure_H(pk);
-        std::vector<pvac_enc_item> items(n);
-        for (size_t i = 0; i < n; ++i) items[i] = pvac_enc_item{its[i].v_lo, its[i].v_hi, its[i].depth_hint, its[i].kind, 0, 0};
+        const std::vector<pvac_enc_item> items = abi_items(its);
         std::vector<uint64_t> hint(n);
         uint64_t ls = 0, es = 0;
         check(pvac_hip_enc_items_caps(ctx_, n, items.data(), &ls, &es, hint.data()));
@@ -958,10 +939,8 @@ public:
             detail::dev_array<uint64_t> d_r(flat.size());
             d_r.upload(flat.data(), flat.size(), stream_);
             detail::batch c;
-            c.d_l_off.alloc(m); c.d_l_cnt.alloc(m); c.d_e_off.alloc(m); c.d_e_cnt.alloc(m);
-            detail::alloc_out(c, m, ls, es, sigma_words(), with_sigma);
-            pvac_ct_batch vc = c.view(with_sigma);
-            vc.n = m;
+            c.alloc_index(m);
+            pvac_ct_batch vc = exec_out(c, m, ls, es, sigma_words(), with_sigma);
             detail::dev_array<uint32_t> st(m);
             check(pvac_hip_enc_items(ctx_, m, sub.data(), d_r.p, flat.size(), &vc, ls, es, with_sigma ? PVAC_ENC_WITH_SIGMA : 0,
                                      st.p));
@@ -1043,18 +1022,14 @@ public:
         if (!n) return {};
         ensure_keys(pk, sk);
         detail::batch x;
-        detail::to_host(cs, sigma_words(), false, x);
-        detail::upload(x, stream_, false);
-        pvac_ct_batch vx = x.view(false);
+        pvac_ct_batch vx = stage(cs, false, x);
         detail::dev_array<uint64_t> R(2 * (x.layers.size() ? x.layers.size() : 1)), out(2 * n);
         detail::dev_array<uint32_t> st(n);
         check(pvac_hip_base_R(ctx_, &vx, R.p));
         check(pvac_hip_dec_value(ctx_, &vx, R.p, out.p, st.p));
         std::vector<uint64_t> o(2 * n);
-        std::vector<uint32_t> s(n);
         out.download(o.data(), 2 * n, stream_);
-        st.download(s.data(), n, stream_);
-        detail::hip_ok(hipStreamSynchronize(stream_), "sync");
+        const detail::hvec<uint32_t> s = detail::d2h(st.p, n, stream_);
         std::vector<FpT> r(n);
         for (size_t i = 0; i < n; ++i) {
             if (s[i] == 1) throw Error(PVAC_EINVAL, "dec_value: layer graph has a cycle or a bad parent");
@@ -1081,12 +1056,10 @@ public:
         const size_t n = cs.size();
         if (!n) return {};
         detail::batch x;
-        detail::to_host(cs, sigma_words(), true, x);
-        detail::upload(x, stream_, true);
-        pvac_ct_batch vx = x.view(true);
+        pvac_ct_batch vx = stage(cs, true, x);
         detail::dev_array<uint64_t> ones(n);
         check(pvac_hip_sigma_popcount(ctx_, &vx, ones.p));
-        const detail::hvec<uint64_t> o = detail::d2h_u64(ones.p, n, stream_);
+        const detail::hvec<uint64_t> o = detail::d2h(ones.p, n, stream_);
         std::vector<double> d(n, 0.0);
         for (size_t i = 0; i < n; ++i) {
             if (cs[i]->E.empty()) continue;
@@ -1104,9 +1077,7 @@ public:
         if (!n) return {};
         ensure_ubk(pk);
         detail::batch x;
-        detail::to_host(cs, sigma_words(), true, x);
-        detail::upload(x, stream_, true);
-        pvac_ct_batch vx = x.view(true);
+        pvac_ct_batch vx = stage(cs, true, x);
         check(pvac_hip_ubk_apply(ctx_, &vx, nullptr));
         return detail::from_device<CipherT>(x, n, x.layers.size(), x.meta.size(), prm_.m_bits, true, stream_);
     }
@@ -1117,18 +1088,11 @@ public:
         const size_t n = cs.size();
         if (!n) return {};
         detail::batch x, c;
-        detail::to_host(cs, sigma_words(), true, x);
-        detail::upload(x, stream_, true);
-        pvac_ct_batch vx = x.view(true);
-        c.d_l_off.alloc(n); c.d_l_cnt.alloc(n); c.d_e_off.alloc(n); c.d_e_cnt.alloc(n);
-        pvac_ct_batch vc{};
-        vc.l_off = c.d_l_off.p; vc.l_cnt = c.d_l_cnt.p; vc.e_off = c.d_e_off.p; vc.e_cnt = c.d_e_cnt.p;
+        pvac_ct_batch vx = stage(cs, true, x);
+        pvac_ct_batch vc = plan_out(c, n);
         pvac_hip_plan plan{};
         check(pvac_hip_compact_plan(ctx_, &vx, &vc, &plan));
-        detail::alloc_out(c, n, std::max<uint64_t>(plan.total_layer_slots, 1), std::max<uint64_t>(plan.total_edge_slots, 1),
-                          sigma_words(), true);
-        vc = c.view(true);
-        vc.n = n;
+        vc = exec_out(c, n, plan.total_layer_slots, plan.total_edge_slots, sigma_words(), true, 1);
         check(pvac_hip_compact_exec(ctx_, &plan, &vx, &vc));
         return detail::from_device<CipherT>(c, n, plan.total_layer_slots, plan.total_edge_slots, prm_.m_bits, true,
                                             stream_);
@@ -1152,8 +1116,7 @@ public:
         std::vector<const CipherT*> pp;
         for (const CipherT& z : pool) pp.push_back(&z);
         detail::batch p;
-        detail::to_host(pp, sigma_words(), true, p);
-        detail::upload(p, stream_, true);
+        const pvac_ct_batch vp = stage(pp, true, p);
         std::vector<CipherT> out(n);
         std::vector<uint32_t> iters(n, 0), drawn(n, 0);
         std::vector<uint64_t> picks(8 * n, 0);
@@ -1168,7 +1131,7 @@ public:
                 std::memcpy(&sub_picks[8 * j], &picks[8 * pending[j]], 64);
             }
             std::vector<uint32_t> sub_iters(m, 0);
-            std::vector<CipherT> sub_out = recrypt_run<CipherT>(p, sub, sub_picks, sub_iters);
+            std::vector<CipherT> sub_out = recrypt_run<CipherT>(vp, sub, sub_picks, sub_iters);
             std::vector<size_t> next;
             for (size_t j = 0; j < m; ++j) {
                 const size_t i = pending[j];
@@ -1211,14 +1174,10 @@ public:
             std::vector<const CipherT*> sub(m);
             for (size_t j = 0; j < m; ++j) sub[j] = cs[ids[kind][j]];
             detail::batch x;
-            detail::to_host(sub, sigma_words(), kind == 1, x);
-            detail::upload(x, stream_, kind == 1);
-            pvac_ct_batch vx = x.view(kind == 1);
+            pvac_ct_batch vx = stage(sub, kind == 1, x);
             detail::dev_array<uint8_t> dig(32 * m);
             check(pvac_hip_commit_ct(ctx_, &vx, dig.p));
-            std::vector<uint8_t> h(32 * m);
-            dig.download(h.data(), h.size(), stream_);
-            detail::hip_ok(hipStreamSynchronize(stream_), "sync");
+            const detail::hvec<uint8_t> h = detail::d2h(dig.p, 32 * m, stream_);
             for (size_t j = 0; j < m; ++j) std::memcpy(out[ids[kind][j]].data(), &h[32 * j], 32);
         }
         return out;
@@ -1228,9 +1187,7 @@ public:
     template <class PubKeyT>
     void ensure_powg(const PubKeyT& pk) {
         if (keys_ready_ || powg_ready_) return;
-        std::vector<uint64_t> pg(2 * pk.powg_B.size());
-        for (size_t i = 0; i < pk.powg_B.size(); ++i) { pg[2 * i] = pk.powg_B[i].lo; pg[2 * i + 1] = pk.powg_B[i].hi; }
-        check(pvac_hip_ctx_set_powg(ctx_, pg.data(), (uint32_t)pk.powg_B.size()));
+        set_powg(pk);
         powg_ready_ = true;
     }
 
@@ -1274,12 +1231,10 @@ public:
         std::vector<const CipherT*> sub(m);
         for (size_t j = 0; j < m; ++j) sub[j] = cs[ids[j]];
         detail::batch x;
-        detail::to_host(sub, sigma_words(), true, x);
-        detail::upload(x, stream_, true);
-        pvac_ct_batch vx = x.view(true);
+        pvac_ct_batch vx = stage(sub, true, x);
         detail::dev_array<uint64_t> hist(256 * m);
         check(pvac_hip_sigma_bytehist(ctx_, &vx, hist.p));
-        const detail::hvec<uint64_t> h = detail::d2h_u64(hist.p, 256 * m, stream_);
+        const detail::hvec<uint64_t> h = detail::d2h(hist.p, 256 * m, stream_);
         for (size_t j = 0; j < m; ++j) H[ids[j]] = shannon_of_counts(&h[256 * j]);
         return H;
     }
@@ -1293,16 +1248,14 @@ public:
         if (!n) return out;
         ensure_powg(pk);
         detail::batch x;
-        detail::to_host(cs, sigma_words(), false, x);
-        detail::upload(x, stream_, false);
-        pvac_ct_batch vx = x.view(false);
+        pvac_ct_batch vx = stage(cs, false, x);
         const size_t slots = x.layers.size();
         detail::dev_array<uint64_t> g(2 * (slots ? slots : 1));
         detail::dev_array<uint32_t> st(n);
         check(pvac_hip_layer_gsum(ctx_, &vx, g.p, st.p));
         std::vector<uint32_t> s(n);
         st.download(s.data(), n, stream_);
-        const detail::hvec<uint64_t> w = detail::d2h_u64(g.p, 2 * slots, stream_);
+        const detail::hvec<uint64_t> w = detail::d2h(g.p, 2 * slots, stream_);
         for (size_t i = 0; i < n; ++i) {
             if (s[i]) throw Error(PVAC_EINVAL, "agg_layer_gsum: an edge's idx is out of range");
             out[i].resize(cs[i]->L.size());
@@ -1352,10 +1305,8 @@ public:
         device_batch out;
         out.sigma_bits = info.sigma_bits;
         detail::batch& b = out.arrays;
-        b.d_l_off.alloc(n); b.d_l_cnt.alloc(n); b.d_e_off.alloc(n); b.d_e_cnt.alloc(n);
-        detail::alloc_out(b, n, info.total_layers, info.total_edges, info.sigma_words, sig);
-        pvac_ct_batch v = b.view(sig);
-        v.n = n;
+        b.alloc_index(n);
+        pvac_ct_batch v = exec_out(b, n, info.total_layers, info.total_edges, info.sigma_words, sig);
         check(pvac_hip_ct_image_parse(ctx_, image.p, file.size(), dpos.p, n, info.sigma_bits, &v, info.total_layers,
                                       info.total_edges, nullptr));
         return out;
@@ -1407,14 +1358,10 @@ private:
         G.pick_src = pick_src;
         G.pick_idx = pick_idx;
         detail::batch& b = out.arrays;
-        b.d_l_off.alloc(m); b.d_l_cnt.alloc(m); b.d_e_off.alloc(m); b.d_e_cnt.alloc(m);
-        pvac_ct_batch v{};
-        v.l_off = b.d_l_off.p; v.l_cnt = b.d_l_cnt.p; v.e_off = b.d_e_off.p; v.e_cnt = b.d_e_cnt.p;
+        pvac_ct_batch v = plan_out(b, m);
         uint64_t tot[2] = {0, 0};
         check(pvac_hip_batch_gather_plan(ctx_, &G, &v, tot));
-        detail::alloc_out(b, m, tot[0], tot[1], sw, sig);
-        v = b.view(sig);
-        v.n = m;
+        v = exec_out(b, m, tot[0], tot[1], sw, sig);
         check(pvac_hip_batch_gather_exec(ctx_, &G, &v, tot[0], tot[1]));
         // the pick lists and the views die with this call: the rows must have been read by then
         detail::hip_ok(hipStreamSynchronize(stream_), "sync");
@@ -1432,24 +1379,68 @@ private:
         return f;
     }
 
-    // one pvac_hip_ct_recrypt_plan + _exec over cs with 8 picks per cipher (p: the uploaded pool)
+    // Ciphers -> x, resident on the device (the copies are asynchronous on stream_), and its view. The
+    // one flag decides whether the host image, the upload and the view carry sigma.
     template <class CipherT>
-    std::vector<CipherT> recrypt_run(detail::batch& p, const std::vector<const CipherT*>& cs,
+    pvac_ct_batch stage(const std::vector<const CipherT*>& cs, bool with_sigma, detail::batch& x) {
+        detail::to_host(cs, sigma_words(), with_sigma, x);
+        detail::upload(x, stream_, with_sigma);
+        return x.view(with_sigma);
+    }
+
+    // The output batch of a plan / exec pair, in two steps around the two ABI calls. Before the plan:
+    // the per-cipher arrays it fills, as the view it takes.
+    static pvac_ct_batch plan_out(detail::batch& c, size_t n, uint32_t words = 0) {
+        c.alloc_index(n);
+        return c.plan_view(words);
+    }
+    // After it (or, where an operation has no plan, after alloc_index): rows at the totals, as the view
+    // exec writes. min_slots = 1 where a plan may total 0 (compact, recrypt): the allocation is sized
+    // for one row then, the download still takes the totals.
+    static pvac_ct_batch exec_out(detail::batch& c, size_t n, uint64_t lslots, uint64_t eslots, uint32_t words,
+                                  bool with_sigma, uint64_t min_slots = 0) {
+        c.alloc_rows(n, std::max(lslots, min_slots), std::max(eslots, min_slots), words, with_sigma);
+        return c.out_view(n, with_sigma);
+    }
+
+    template <class PubKeyT>
+    void set_powg(const PubKeyT& pk) {
+        std::vector<uint64_t> pg(2 * pk.powg_B.size());
+        for (size_t i = 0; i < pk.powg_B.size(); ++i) { pg[2 * i] = pk.powg_B[i].lo; pg[2 * i + 1] = pk.powg_B[i].hi; }
+        check(pvac_hip_ctx_set_powg(ctx_, pg.data(), (uint32_t)pk.powg_B.size()));
+    }
+
+    // plan_noise's Params fields (core/types.hpp:48-50), read on every call like the reference
+    template <class PubKeyT>
+    void set_noise(const PubKeyT& pk) {
+        check(pvac_hip_ctx_set_noise(ctx_, (double)pk.prm.noise_entropy_bits, (double)pk.prm.tuple2_fraction,
+                                     (double)pk.prm.depth_slope_bits));
+    }
+
+    static std::vector<pvac_enc_item> abi_items(const std::vector<EncItem>& its) {
+        std::vector<pvac_enc_item> items(its.size());
+        for (size_t i = 0; i < its.size(); ++i)
+            items[i] = pvac_enc_item{its[i].v_lo, its[i].v_hi, its[i].depth_hint, its[i].kind, 0, 0};
+        return items;
+    }
+
+    // the batched ct_mul's engine-owned arrays
+    void release_mul() {
+        mul_a_.release(); mul_b_.release(); mul_c_.release(); mul_p_.release();
+        mul_nonces_.release(); mul_salts_.release(); mul_status_.release();
+    }
+
+    // one pvac_hip_ct_recrypt_plan + _exec over cs with 8 picks per cipher (vp: the uploaded pool)
+    template <class CipherT>
+    std::vector<CipherT> recrypt_run(const pvac_ct_batch& vp, const std::vector<const CipherT*>& cs,
                                      const std::vector<uint64_t>& picks, std::vector<uint32_t>& iters) {
         const size_t n = cs.size();
         detail::batch x, c;
-        detail::to_host(cs, sigma_words(), true, x);
-        detail::upload(x, stream_, true);
-        pvac_ct_batch vx = x.view(true), vp = p.view(true);
-        c.d_l_off.alloc(n); c.d_l_cnt.alloc(n); c.d_e_off.alloc(n); c.d_e_cnt.alloc(n);
-        pvac_ct_batch vc{};
-        vc.l_off = c.d_l_off.p; vc.l_cnt = c.d_l_cnt.p; vc.e_off = c.d_e_off.p; vc.e_cnt = c.d_e_cnt.p;
+        pvac_ct_batch vx = stage(cs, true, x);
+        pvac_ct_batch vc = plan_out(c, n);
         pvac_hip_plan plan{};
         check(pvac_hip_ct_recrypt_plan(ctx_, &vx, &vp, &vc, &plan));
-        detail::alloc_out(c, n, std::max<uint64_t>(plan.total_layer_slots, 1), std::max<uint64_t>(plan.total_edge_slots, 1),
-                          sigma_words(), true);
-        vc = c.view(true);
-        vc.n = n;
+        vc = exec_out(c, n, plan.total_layer_slots, plan.total_edge_slots, sigma_words(), true, 1);
         iters.assign(n, 0);
         check(pvac_hip_ct_recrypt_exec(ctx_, &plan, &vx, &vp, picks.data(), &vc, iters.data()));
         return detail::from_device<CipherT>(c, n, plan.total_layer_slots, plan.total_edge_slots, prm_.m_bits, true,
@@ -1466,11 +1457,9 @@ private:
         d_v.upload(vs.data(), n, stream_);
         d_r.upload(draws.data(), draws.size(), stream_);
         detail::batch c;
-        c.d_l_off.alloc(n); c.d_l_cnt.alloc(n); c.d_e_off.alloc(n); c.d_e_cnt.alloc(n);
+        c.alloc_index(n);
         const uint64_t lslots = (uint64_t)n * lpv, eslots = (uint64_t)n * epv;
-        detail::alloc_out(c, n, lslots, eslots, sigma_words(), with_sigma);
-        pvac_ct_batch vc = c.view(with_sigma);
-        vc.n = n;
+        pvac_ct_batch vc = exec_out(c, n, lslots, eslots, sigma_words(), with_sigma);
         detail::dev_array<uint32_t> st(n);
         check(pvac_hip_enc_value_depth(ctx_, n, d_v.p, d_r.p, stride, depth_hint, &vc,
                                        with_sigma ? PVAC_ENC_WITH_SIGMA : 0, st.p));

@@ -1,8 +1,9 @@
 // host_arrays_check.cpp — CPU-only checks of the C++ adapter's host side (include/pvac_hip.hpp):
 // the AoS <-> SoA conversion of reference-shaped Ciphers (detail::to_host / detail::convert_host,
-// with and without sigma, over enough ciphers to take the threaded path) and the page-locked host
+// with and without sigma, over enough ciphers to take the threaded path), the page-locked host
 // arrays' fallback: without a GPU the runtime refuses to pin, so pinned_batch arrays must come from
-// ordinary memory and go back to it (pinned_registry stays empty). Exit 0 = every check passed.
+// ordinary memory and go back to it (pinned_registry stays empty), and the batch's views: every
+// device array in the pvac_ct_batch field of its own name. Exit 0 = every check passed.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -121,6 +122,37 @@ int main() {
         auto& reg = pvac_hip::detail::pinned_registry::get();
         std::lock_guard<std::mutex> g(reg.mu);
         CHECK(reg.pinned.empty(), "%zu pinned allocations left registered", reg.pinned.size());
+    }
+    {   // the batch's array list: nine made-up device addresses, each in the view field of its own name
+        // and in no other (they are distinct), whichever view is asked for; nothing is dereferenced
+        uint64_t slot[8];
+        pvac_layer lay;
+        pvac_hip::detail::batch b;
+        b.d_l_off.p = &slot[0]; b.d_l_cnt.p = &slot[1]; b.d_e_off.p = &slot[2]; b.d_e_cnt.p = &slot[3];
+        b.d_layers.p = &lay;
+        b.d_meta.p = &slot[4]; b.d_w_lo.p = &slot[5]; b.d_w_hi.p = &slot[6]; b.d_sigma.p = &slot[7];
+        b.l_cnt.resize(5);
+        b.sigma_words = 7;
+        auto expect = [&](const pvac_ct_batch& v, uint64_t n, bool rows, bool sigma, uint32_t words, const char* what) {
+            CHECK(v.n == n && v.sigma_words == words, "%s: n %llu, sigma_words %u", what, (unsigned long long)v.n,
+                  v.sigma_words);
+            CHECK(v.l_off == &slot[0] && v.l_cnt == &slot[1] && v.e_off == &slot[2] && v.e_cnt == &slot[3],
+                  "%s: per-cipher arrays", what);
+            CHECK(v.layers == (rows ? &lay : nullptr) && v.meta == (rows ? &slot[4] : nullptr) &&
+                      v.w_lo == (rows ? &slot[5] : nullptr) && v.w_hi == (rows ? &slot[6] : nullptr),
+                  "%s: rows", what);
+            CHECK(v.sigma == (sigma ? &slot[7] : nullptr), "%s: sigma", what);
+        };
+        expect(b.view(true), 5, true, true, 7, "view(true)");
+        expect(b.view(false), 5, true, false, 7, "view(false)");
+        expect(b.plan_view(), 0, false, false, 0, "plan_view()");
+        expect(b.plan_view(128), 0, false, false, 128, "plan_view(128)");
+        expect(b.out_view(3, true), 3, true, true, 7, "out_view(3, true)");
+        expect(b.out_view(9, false), 9, true, false, 7, "out_view(9, false)");
+        // the addresses were never allocations: the batch must not free them
+        b.d_l_off.p = b.d_l_cnt.p = b.d_e_off.p = b.d_e_cnt.p = nullptr;
+        b.d_layers.p = nullptr;
+        b.d_meta.p = b.d_w_lo.p = b.d_w_hi.p = b.d_sigma.p = nullptr;
     }
     if (g_fail) return 1;
     std::printf("host_arrays_check: ok\n");

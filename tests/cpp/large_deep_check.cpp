@@ -1,7 +1,7 @@
 // large_deep_check.cpp — csrc/large_plan.hpp for deep pairs (Lc = |A.L| + |B.L| + |A.L||B.L| above
 // kLargeLayersMax, accepted under a raised layer limit) without a GPU: the limit argument of
 // build_large_desc, the scratch layout of a deep pair, and the cut that keeps deep and ordinary pairs in
-// sub-batches of their own. Host code only; built with ASan + UBSan by tests/cpp/deep.mk.
+// sub-batches of their own. Host code only; built with ASan + UBSan by tests/cpp/Makefile.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>

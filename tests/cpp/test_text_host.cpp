@@ -1,5 +1,5 @@
 // test_text_host.cpp — pvac_text_pack / pvac_text_unpack (csrc/rt_text.cpp) as a stand-alone host
-// program: built with -fsanitize=address,undefined by text.mk (exact-size heap buffers, so a byte
+// program: built with -fsanitize=address,undefined by the Makefile (exact-size heap buffers, so a byte
 // past an end is reported) and run by tests/test_text_host.py. No GPU, no libpvac_hip.so.
 #include <cstdint>
 #include <cstdio>

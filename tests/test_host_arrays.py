@@ -1,7 +1,8 @@
 """The C++ adapter's host side without a GPU (tests/cpp/host_arrays_check.cpp): reference-shaped
 Ciphers through to_host / convert_host round trip exactly (ragged shapes, with and without
 sigma, plain and page-locked host arrays), and the page-locked arrays fall back to ordinary
-memory when the runtime refuses to pin, leaving nothing registered."""
+memory when the runtime refuses to pin, leaving nothing registered; every view of a batch puts each
+device array in the pvac_ct_batch field of its own name."""
 import os
 import subprocess
 

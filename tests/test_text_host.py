@@ -1,7 +1,7 @@
 """pvac_text_pack / pvac_text_unpack (csrc/rt_text.cpp; reference utils/text.hpp:15-37, 63-87): host
 memory, no context. Through libpvac_hip.so against the Python restatement in tests/text_model.py, and
 as the stand-alone program tests/cpp/test_text_host.cpp built with AddressSanitizer and UBSan
-(tests/cpp/text.mk). CPU only."""
+(tests/cpp/Makefile). CPU only."""
 import ctypes as C
 import os
 import subprocess
@@ -72,7 +72,7 @@ def test_flags_and_capacities(lib):
 def test_standalone_program_under_sanitizers():
     """tests/cpp/test_text_host.cpp: its own main over the same helpers, compiled with
     -fsanitize=address,undefined, run as a program."""
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp"), "-f", "text.mk", "build/test_text_host"])
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp"), "build/test_text_host"])
     r = subprocess.run([EXE], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "text host checks passed" in r.stdout
