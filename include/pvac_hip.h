@@ -675,8 +675,10 @@ int pvac_hip_enc_value(pvac_hip_ctx* ctx, size_t n, const uint64_t* values, cons
                        pvac_ct_batch* C, uint32_t flags, uint32_t* status);
 /* enc_value_depth(pk, sk, v, depth_hint) (ops/encrypt.hpp:281-287): as pvac_hip_enc_value with the
  * noise plan of depth_hint (plan_noise, encrypt.hpp:16-27: more Z2 / Z3 groups as the hint grows;
- * supported while 8 + 2 Z2 + 3 Z3 <= 256, i.e. depth_hint <= 124 with the default Params, else
- * PVAC_ENOSYS; the Params noise fields from pvac_hip_ctx_set_noise). values[i] = 0 gives
+ * supported while 8 + 2 Z2 + 3 Z3 is within the context's plan limit, pvac_hip_ctx_set_enc_plan_limit:
+ * 256 by default, i.e. depth_hint <= 124 with the default Params, else PVAC_ENOSYS; above 256 edges the
+ * values run as VALUE items of pvac_hip_enc_items on its wide route, with the same output layout;
+ * the Params noise fields from pvac_hip_ctx_set_noise). values[i] = 0 gives
  * enc_zero_depth(pk, sk, depth_hint) (encrypt.hpp:293-298) byte for byte: fp_add(0, mask) is mask and
  * the draws are the same. Size outputs and rnd_stride with
  * pvac_hip_enc_caps_depth. */
@@ -700,10 +702,41 @@ int pvac_hip_enc_value_depth(pvac_hip_ctx* ctx, size_t n, const uint64_t* values
  * C->sigma with PVAC_ENC_WITH_SIGMA) edge_cap slots. status (DEVICE, n u32) as for pvac_hip_enc_value:
  * 0 ok, 1 the item's segment ran out (its rows are meaningless; its neighbours are unaffected), 2 a
  * merged group cancelled exactly. Before anything is launched or written: PVAC_EINVAL for an unknown
- * kind or a draw range outside rnd_words, PVAC_ENOSYS for a plan beyond 256 pre-merge edges per half
- * (depth hint > 124 with the default Params), PVAC_ENOMEM when layer_cap / edge_cap are too small.
- * Needs what pvac_hip_enc_value needs. Synchronises once (the item records' upload); the kernels are
- * enqueued. pvac_hip_enc_value(_depth) keep their own kernels. */
+ * kind or a draw range outside rnd_words, PVAC_ENOSYS for a plan beyond the context's plan limit (by
+ * default 256 pre-merge edges per half: depth hint > 124 with the default Params), PVAC_ENOMEM when
+ * layer_cap / edge_cap are too small.
+ * Needs what pvac_hip_enc_value needs. Synchronises once per sub-batch (the item records' upload); the
+ * kernels are enqueued. pvac_hip_enc_value(_depth) keep their own kernels up to 256 edges. */
+/* The plan limit of a context: the most pre-merge edges per half (8 + 2 Z2 + 3 Z3) an encryption may
+ * plan. Every encryption entry (enc_caps_depth, enc_value_depth, enc_items_caps, enc_items) refuses a
+ * plan above it with PVAC_ENOSYS before anything is launched or written. Up to 256 edges an item runs
+ * the narrow kernels (k_enc.hip, k_enc_items.hip); above, the wide route (k_enc_wide.hip), which keeps
+ * its per-half key tables in global scratch, is linear in the plan and gives what the reference gives
+ * from the same draws. The reference has no bound: enc_text uses depth hint 2 + b for block b, so with
+ * the default Params a message of 1,846 bytes or more needs hint 125 (257 edges). The default of 256
+ * is kept on purpose: scratch is about 1 KB per pre-merge edge with sigma (m_bits / 8 bytes of sigma
+ * row plus 54 bytes of rows, 70 on the wide route), and a text's pre-merge edges grow with the square
+ * of its length (17,480 for 1,860 bytes, 975,452 for 15,000), so a caller raises the limit knowing what
+ * a message costs. set: PVAC_EINVAL outside [PVAC_ENC_PLAN_LIMIT_DEFAULT, PVAC_ENC_PLAN_LIMIT_MAX].
+ * A call runs in sub-batches of consecutive items, cut where their pre-merge edges would pass the
+ * context's budget (default 2^22; an item above it runs alone; set: PVAC_EINVAL for 0): the scratch
+ * arena is sized by the largest sub-batch, and results do not depend on the cuts. A call of narrow
+ * items within the budget is one sub-batch and launches what it always did.
+ * PVAC_ENC_WIDE_ALL (pvac_hip_enc_items' flags) sends every item down the wide route, whatever its
+ * plan: for tests and measurements, the two routes agree on every plan both can run.
+ * draws_hint of a plan above 256 edges carries a slack of max(146, ceil(6 (28 + Z2 + 3 Z3) / B)) draws
+ * per half in place of 32 (derived in csrc/enc_wide.hpp: expected rejections grow with the plan).
+ * pvac_hip_enc_path_count, since the context was created: out[0] / out[1] = items run by the narrow /
+ * the wide route, out[2] = sub-batches, out[3] = runs (an enc_items call with n > 0, an enc_value(_depth) call). */
+#define PVAC_ENC_WIDE_ALL 0x2u
+#define PVAC_ENC_PLAN_LIMIT_DEFAULT 256u
+#define PVAC_ENC_PLAN_LIMIT_MAX (1u << 24)
+#define PVAC_ENC_BUDGET_DEFAULT (1ull << 22)
+int pvac_hip_ctx_set_enc_plan_limit(pvac_hip_ctx* ctx, uint32_t max_pre_edges); /* DEFAULT..MAX, else PVAC_EINVAL */
+int pvac_hip_ctx_enc_plan_limit(pvac_hip_ctx* ctx, uint32_t* out);
+int pvac_hip_ctx_set_enc_budget(pvac_hip_ctx* ctx, uint64_t pre_edges);
+int pvac_hip_ctx_enc_budget(pvac_hip_ctx* ctx, uint64_t* out);
+int pvac_hip_enc_path_count(pvac_hip_ctx* ctx, uint64_t out[4]);
 #define PVAC_ENC_ITEM_FP    0u  /* enc_fp_depth(pk, sk, Fp{v_lo, v_hi}, depth_hint), encrypt.hpp:162-258: 1 BASE layer */
 #define PVAC_ENC_ITEM_VALUE 1u  /* enc_value_depth(pk, sk, v_lo, depth_hint), :281-287: 2 layers (v_lo = 0: enc_zero_depth) */
 typedef struct pvac_enc_item {  /* HOST memory */

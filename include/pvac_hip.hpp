@@ -498,6 +498,19 @@ public:
         return v;
     }
 
+    // The pre-merge edges per half an encryption may plan (pvac_hip_ctx_set_enc_plan_limit:
+    // PVAC_ENC_PLAN_LIMIT_DEFAULT = 256 .. PVAC_ENC_PLAN_LIMIT_MAX). Above 256 an item runs the wide route;
+    // scratch is about 1 KB per pre-merge edge with sigma and a text's edges grow with the square of its
+    // length. The free functions' engine: engine_for(pk).set_enc_plan_limit(n). set_enc_budget: the
+    // pre-merge edges of a sub-batch (PVAC_ENC_BUDGET_DEFAULT).
+    void set_enc_plan_limit(uint32_t max_pre_edges) { check(pvac_hip_ctx_set_enc_plan_limit(ctx_, max_pre_edges)); }
+    uint32_t enc_plan_limit() const {
+        uint32_t v = 0;
+        if (const int rc = pvac_hip_ctx_enc_plan_limit(ctx_, &v)) throw Error(rc, "pvac_hip_ctx_enc_plan_limit");
+        return v;
+    }
+    void set_enc_budget(uint64_t pre_edges) { check(pvac_hip_ctx_set_enc_budget(ctx_, pre_edges)); }
+
     // Wall-clock split of the last batched ct_mul, in seconds: host AoS -> SoA, H2D, plan + nonce
     // draws, exec (+ salts, sigma and the device-side pack of the used rows), D2H, SoA -> AoS.
     struct Phases { double to_soa = 0, h2d = 0, plan = 0, exec = 0, d2h = 0, to_aos = 0; };
@@ -1877,8 +1890,11 @@ CipherT enc_fp_depth(const PubKeyT& pk, const SecKeyT& sk, const FpT& v, int dep
         pk, sk, {Engine::EncItem{PVAC_ENC_ITEM_FP, v.lo, v.hi, depth_hint}}, true, rnd)[0];
 }
 
-// enc_text: the length, then one cipher per 15-byte block with depth hints 2, 3, ...; more than 123
-// blocks (1,845 bytes) under the default noise Params throw Error(PVAC_ENOSYS).
+// enc_text: the length, then one cipher per 15-byte block with depth hints 2, 3, ... At the default plan
+// limit more than 123 blocks (1,845 bytes) under the default noise Params throw Error(PVAC_ENOSYS); raise
+// it with engine_for(pk).set_enc_plan_limit(n) (hint 2 + b needs about 2 (2 + b) + 8 edges) and longer
+// messages run on the wide route. enc_fp_depth, enc_value_depth, enc_zero_depth and make_evalkey follow
+// the same limit.
 template <class CipherT, class PubKeyT, class SecKeyT>
 std::vector<std::vector<CipherT>> enc_text_batch(const PubKeyT& pk, const SecKeyT& sk, const std::vector<std::string>& msgs,
                                                  bool with_sigma = true, const RandomSource& rnd = os_random_u64) {

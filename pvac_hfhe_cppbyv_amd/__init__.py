@@ -33,6 +33,10 @@ CHAIN_IMG_BATCH2 = 0x400
 CHAIN_MAX_DEPTH = 32
 LAYER_LIMIT_DEFAULT, LAYER_LIMIT_MAX = 16384, 1 << 24
 ENC_WITH_SIGMA = 0x1
+ENC_WIDE_ALL = 0x2           # enc_items: every item by the wide route (k_enc_wide.hip)
+ENC_PLAN_LIMIT_DEFAULT = 256  # pre-merge edges per half (pvac_hip_ctx_set_enc_plan_limit)
+ENC_PLAN_LIMIT_MAX = 1 << 24
+ENC_BUDGET_DEFAULT = 1 << 22  # pre-merge edges of a sub-batch
 ENC_ITEM_FP, ENC_ITEM_VALUE = 0, 1
 TEXT_LEN_HI, TEXT_LEN_CLIPPED = 0x1, 0x2
 
@@ -211,6 +215,11 @@ def load_library(path: str = _LIB_PATH) -> C.CDLL:
         "pvac_hip_ctx_set_secret": ([vp, vp, vp, u32, u32, u32, u32], i32),
         "pvac_hip_ctx_set_H_digest": ([vp, vp], i32),
         "pvac_hip_prf": ([vp, i32, C.c_size_t, vp, vp], i32),
+        "pvac_hip_ctx_set_enc_plan_limit": ([vp, u32], i32),
+        "pvac_hip_ctx_enc_plan_limit": ([vp, C.POINTER(u32)], i32),
+        "pvac_hip_ctx_set_enc_budget": ([vp, u64], i32),
+        "pvac_hip_ctx_enc_budget": ([vp, C.POINTER(u64)], i32),
+        "pvac_hip_enc_path_count": ([vp, C.POINTER(u64)], i32),
         "pvac_hip_enc_caps": ([vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)], i32),
         "pvac_hip_enc_value": ([vp, C.c_size_t, vp, vp, u32, C.POINTER(CtBatch), u32, vp], i32),
         "pvac_hip_enc_caps_depth": ([vp, i32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)], i32),
@@ -358,7 +367,8 @@ class Engine:
     """One pvac_hip_ctx on one GPU, bound to torch's current stream on that device."""
 
     def __init__(self, device=0, B=337, m_bits=8192, n_bits=16384, h_col_wt=192, x_col_wt=128, err_wt=128,
-                 edge_budget=1200000, canon_tag=0, lib: C.CDLL | None = None, layer_limit=None):
+                 edge_budget=1200000, canon_tag=0, lib: C.CDLL | None = None, layer_limit=None,
+                 enc_plan_limit=None):
         import torch
         self.torch = torch
         self.lib = lib or load_library()
@@ -373,6 +383,8 @@ class Engine:
         self._check(self.lib.pvac_hip_ctx_set_stream(self.ctx, C.c_void_p(stream.cuda_stream)))
         if layer_limit is not None:
             self.set_layer_limit(layer_limit)
+        if enc_plan_limit is not None:
+            self.set_enc_plan_limit(enc_plan_limit)
 
     def __del__(self):
         try:
@@ -478,11 +490,12 @@ class Engine:
                                                      C.c_void_p(dh.ctypes.data)))
         return ls.value, es.value, dh[:n]
 
-    def enc_items(self, items, rnd, sigma=False, caps=None):
+    def enc_items(self, items, rnd, sigma=False, caps=None, wide_all=False):
         """One launch sequence over a ragged batch: item i = (kind, v, depth_hint, rnd_off, rnd_cnt) is
         enc_fp_depth(v, hint) (ENC_ITEM_FP, one layer) or enc_value_depth(v, hint) (ENC_ITEM_VALUE) from the
         draws rnd[rnd_off : rnd_off + rnd_cnt] (rnd: flat u64 host array or device tensor). caps =
-        (layer_slots, edge_slots) overrides the output sizes. Returns (DeviceBatch, status numpy u32)."""
+        (layer_slots, edge_slots) overrides the output sizes; wide_all sends every item down the wide route
+        (ENC_WIDE_ALL). Returns (DeviceBatch, status numpy u32)."""
         torch = self.torch
         arr = self._items(items)
         n = getattr(arr, "_n", len(arr))
@@ -496,7 +509,8 @@ class Engine:
         status = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
         sc = C_.struct()
         self._check(self.lib.pvac_hip_enc_items(self.ctx, n, C.cast(arr, C.c_void_p), C.c_void_p(rnd.data_ptr()), words,
-                                                C.byref(sc), int(ls), int(es), ENC_WITH_SIGMA if sigma else 0,
+                                                C.byref(sc), int(ls), int(es),
+                                                (ENC_WITH_SIGMA if sigma else 0) | (ENC_WIDE_ALL if wide_all else 0),
                                                 C.c_void_p(status.data_ptr())))
         return C_, status.cpu().numpy().view(np.uint32)[:n]
 
@@ -711,6 +725,35 @@ class Engine:
         v = (C.c_uint64 * 4)()
         self._check(self.lib.pvac_hip_ct_mul_path_count(self.ctx, v))
         return dict(zip(("fresh", "general", "iblk", "direct"), (int(x) for x in v)))
+
+    def set_enc_plan_limit(self, n):
+        """The most pre-merge edges per half an encryption may plan (ENC_PLAN_LIMIT_DEFAULT = 256 ..
+        ENC_PLAN_LIMIT_MAX): above 256 an item runs the wide route. Scratch is about 1 KB per pre-merge edge
+        with sigma and a text's edges grow with the square of its length, hence the default."""
+        self._check(self.lib.pvac_hip_ctx_set_enc_plan_limit(self.ctx, int(n)))
+
+    @property
+    def enc_plan_limit(self):
+        v = C.c_uint32()
+        self._check(self.lib.pvac_hip_ctx_enc_plan_limit(self.ctx, C.byref(v)))
+        return v.value
+
+    def set_enc_budget(self, pre_edges):
+        """Pre-merge edges of an encryption sub-batch (ENC_BUDGET_DEFAULT = 2^22): a call runs in consecutive
+        sub-batches cut at this total, and its scratch is sized by the largest."""
+        self._check(self.lib.pvac_hip_ctx_set_enc_budget(self.ctx, int(pre_edges)))
+
+    @property
+    def enc_budget(self):
+        v = C.c_uint64()
+        self._check(self.lib.pvac_hip_ctx_enc_budget(self.ctx, C.byref(v)))
+        return v.value
+
+    def enc_path_counts(self):
+        """[items by the narrow route, items by the wide route, sub-batches, runs] since the engine was made."""
+        v = (C.c_uint64 * 4)()
+        self._check(self.lib.pvac_hip_enc_path_count(self.ctx, v))
+        return list(v)
 
     def set_layer_limit(self, n):
         """Layers a ct_mul pair may have before compaction (|A.L| + |B.L| + |A.L||B.L|), LAYER_LIMIT_DEFAULT ..

@@ -232,7 +232,7 @@ struct enc_item_rec {         // one per item, built and uploaded by the host
     uint64_t v_lo, v_hi;      // plaintext as given (VALUE items: v_lo)
     uint64_t rnd_off;         // the item's draws: rnd[rnd_off .. rnd_off + rnd_cnt)
     uint32_t rnd_cnt;
-    uint32_t Z2, Z3;          // its noise plan; npre = 8 + 2 Z2 + 3 Z3 <= kEncPreMax
+    uint32_t Z2, Z3;          // its noise plan; npre = 8 + 2 Z2 + 3 Z3 (<= kEncPreMax on the narrow route)
     uint32_t halves;          // 1 = bare enc_fp_depth, 2 = the masked value form
     uint64_t half_off;        // = C.l_off[i]
     uint64_t pre_off;         // = C.e_off[i]
@@ -272,6 +272,51 @@ hipError_t launch_enc_items_weights(const enc_items_args& a, const uint64_t* cor
 // 3. per item: merged groups (fp_add chains, sigma XOR) in shuffled order -> C
 hipError_t launch_enc_items_finish(const enc_items_args& a, const pvac_ct_batch& pre, pvac_ct_batch& C, uint32_t* status,
                                    hipStream_t st);
+
+// ---- the wide route of enc_items (k_enc_wide.hip, enc_wide.hpp): items whose plan has more than
+// kEncPreMax pre-merge edges per half, or every item under PVAC_ENC_WIDE_ALL. A call runs in
+// sub-batches of consecutive items; within one, items, halves and pre-edge slots are numbered from the
+// sub-batch's first (rec.half_off / pre_off are local), the narrow and the wide items have a record
+// list each, and the kernels add base_l / base_e where they write C's offsets. All linear in npre.
+struct enc_wide_args {
+    uint64_t n;                    // wide items of the sub-batch
+    uint64_t n_work, n_fin;
+    const enc_item_rec* recs;      // the wide items' records
+    const uint32_t* item;          // ... and their item index within the sub-batch
+    const uint64_t* work;          // half << 32 | group (as enc_items_args::work, wider)
+    const uint64_t* fin;           // half << 32 | first output slot of a chunk of kEncWideFinChunk
+    const uint32_t* half_item;     // per half of the sub-batch: item << 1 | h
+    const uint64_t* rnd;
+    const uint64_t* powg;
+    uint64_t canon;
+    uint64_t base_l, base_e;       // the sub-batch's first layer and edge slot in C
+    uint32_t B;
+    uint32_t pre_base;             // the wide items' first entry in the pre-merge batch's index arrays
+    enc_half_hdr* hdr;             // [halves of the sub-batch]
+    uint32_t* key;                 // [pre-edge slots] as enc_items_args
+    uint64_t *salt, *rlo, *rhi;
+    uint32_t *occ, *ord;           // ... occurrence number of an edge within its key; edges sorted by key, stable
+    uint32_t *gstart, *slot;       // ... per group rank its first entry in ord; output slot -> group rank
+    uint32_t* tab;                 // [2 n][2 B] key tables, zeroed before the replay
+    uint64_t* dlast;               // [halves][2] the last noise group's Delta
+};
+// 1. per item, one lane: the draws in order, occurrence numbers and key counts, the shuffle, PRF
+//    requests, the pre-merge batch `pre`, C's index entries (at the item's place; C's index arrays and
+//    status start at the sub-batch's first item) and status 0 / 1
+hipError_t launch_enc_wide_replay(const enc_wide_args& a, prf_request* req, pvac_ct_batch& pre, pvac_ct_batch& C,
+                                  uint32_t* status, hipStream_t st);
+// 2. per half, one workgroup: ranks and segment starts by a scan of the key table, then the stable sort
+hipError_t launch_enc_wide_order(const enc_wide_args& a, hipStream_t st);
+// 3. the last group's Delta once per half, then one thread per (half, group) as launch_enc_items_weights
+hipError_t launch_enc_wide_weights(const enc_wide_args& a, const uint64_t* cores, pvac_ct_batch& pre, hipStream_t st);
+// 4. per output edge, one wave: the fp_add chain over its segment, the sigma XOR, status 2. C's edge and
+//    layer arrays start at the sub-batch's first slot.
+hipError_t launch_enc_wide_finish(const enc_wide_args& a, const pvac_ct_batch& pre, pvac_ct_batch& C, uint32_t* status,
+                                  hipStream_t st);
+// the narrow items of a mixed sub-batch: index entries and status from their compact places tmp[t]
+// to item nid[t] of C / status, offsets moved by base_l / base_e
+hipError_t launch_enc_scatter_index(uint64_t n, const uint32_t* nid, const pvac_ct_batch& tmp, const uint32_t* tmp_status,
+                                    uint64_t base_l, uint64_t base_e, pvac_ct_batch& C, uint32_t* status, hipStream_t st);
 
 // ---- dec_value (k_dec.hip):BASE-layer R supplied, PROD R tree, inversions, signed edge sum
 size_t dec_scratch_bytes(uint64_t total_layers);

@@ -193,6 +193,9 @@ struct pvac_hip_ctx {
         double noise_bits = 120.0, noise_t2 = 0.55, noise_slope = 16.0;   // Params noise fields (enc plan_noise)
         pvhip::dev_buf<uint8_t> dec_scratch;
         pvhip::dev_buf<uint64_t> dec_roff;
+        uint32_t enc_plan_limit = PVAC_ENC_PLAN_LIMIT_DEFAULT;   // pvac_hip_ctx_set_enc_plan_limit
+        uint64_t enc_budget = PVAC_ENC_BUDGET_DEFAULT;           // pre-merge edges of a sub-batch
+        uint64_t enc_path[4] = {};   // items narrow / wide, sub-batches and calls (pvac_hip_enc_path_count)
     } prf;
     struct {   // ct_recrypt and its parts (rt_recrypt.cpp, k_recrypt.hip)
         pvhip::dev_buf<uint32_t> ubk_perm;           // pk.ubk as a gather: perm[inv[src]] = src (set_ubk)

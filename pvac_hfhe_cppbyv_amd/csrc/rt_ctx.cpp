@@ -159,6 +159,40 @@ int pvac_hip_deep_path_count(pvac_hip_ctx* c, uint64_t out[2]) {
     return PVAC_OK;
 }
 
+int pvac_hip_ctx_set_enc_plan_limit(pvac_hip_ctx* c, uint32_t max_pre_edges) try {
+    if (!c) return PVAC_EINVAL;
+    if (max_pre_edges < PVAC_ENC_PLAN_LIMIT_DEFAULT || max_pre_edges > PVAC_ENC_PLAN_LIMIT_MAX)
+        return fail(c, PVAC_EINVAL, "ctx_set_enc_plan_limit: the limit lies in [" + std::to_string(PVAC_ENC_PLAN_LIMIT_DEFAULT) +
+                                        ", " + std::to_string(PVAC_ENC_PLAN_LIMIT_MAX) + "]");
+    c->prf.enc_plan_limit = max_pre_edges;
+    return PVAC_OK;
+} catch (...) { return caught(c, "ctx_set_enc_plan_limit"); }
+
+int pvac_hip_ctx_enc_plan_limit(pvac_hip_ctx* c, uint32_t* out) {
+    if (!c || !out) return PVAC_EINVAL;
+    *out = c->prf.enc_plan_limit;
+    return PVAC_OK;
+}
+
+int pvac_hip_ctx_set_enc_budget(pvac_hip_ctx* c, uint64_t pre_edges) {
+    if (!c) return PVAC_EINVAL;
+    if (!pre_edges) return fail(c, PVAC_EINVAL, "ctx_set_enc_budget: a sub-batch holds at least one pre-merge edge");
+    c->prf.enc_budget = pre_edges;
+    return PVAC_OK;
+}
+
+int pvac_hip_ctx_enc_budget(pvac_hip_ctx* c, uint64_t* out) {
+    if (!c || !out) return PVAC_EINVAL;
+    *out = c->prf.enc_budget;
+    return PVAC_OK;
+}
+
+int pvac_hip_enc_path_count(pvac_hip_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return PVAC_EINVAL;
+    for (int k = 0; k < 4; ++k) out[k] = c->prf.enc_path[k];
+    return PVAC_OK;
+}
+
 const char* pvac_hip_last_error(pvac_hip_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 int pvac_hip_timing_enable(pvac_hip_ctx* c, int on) try {

@@ -3,6 +3,7 @@
 #include <cmath>
 
 #include "ctx.hpp"
+#include "enc_wide.hpp"
 #include "sha256.hpp"
 
 using namespace pvhip;
@@ -158,6 +159,20 @@ void plan_noise(const pvac_hip_ctx* c, int depth, uint32_t& z2, uint32_t& z3) {
     z2 = (uint32_t)a;
     z3 = (uint32_t)b;
 }
+// a plan above the context's limit (pvac_hip_ctx_set_enc_plan_limit) is refused before anything happens
+bool plan_over(const pvac_hip_ctx* c, uint32_t z2, uint32_t z3) { return enc_npre(z2, z3) > c->prf.enc_plan_limit; }
+int plan_refused(pvac_hip_ctx* c, const char* who) {   // PVAC_ENOSYS with the message that names the limit
+    if (c->prf.enc_plan_limit == kEncPlanLimitDefault)
+        return fail(c, PVAC_ENOSYS, std::string(who) + ": noise plan beyond 256 pre-merge edges per half (depth hint > 124 with the default Params)");
+    return fail(c, PVAC_ENOSYS, std::string(who) + ": noise plan beyond " + std::to_string(c->prf.enc_plan_limit) +
+                                    " pre-merge edges per half (the context's plan limit, pvac_hip_ctx_set_enc_plan_limit)");
+}
+struct item_plan {
+    uint32_t z2, z3, npre, halves;
+};
+// pvac_hip_enc_items after its argument checks: plans within the limit, capacities checked
+int run_enc_items(pvac_hip_ctx* c, size_t n, const pvac_enc_item* items, const std::vector<item_plan>& plans, const uint64_t* rnd,
+                  pvac_ct_batch* C, uint32_t flags, uint32_t* status);
 }  // namespace
 
 int pvac_hip_enc_caps(pvac_hip_ctx* c, uint32_t* layers_per_value, uint32_t* edges_per_value, uint32_t* draws_hint) {
@@ -169,13 +184,13 @@ int pvac_hip_enc_caps_depth(pvac_hip_ctx* c, int depth_hint, uint32_t* layers_pe
     if (!c) return PVAC_EINVAL;
     uint32_t z2, z3;
     plan_noise(c, depth_hint, z2, z3);
-    if ((uint64_t)8 + 2ull * z2 + 3ull * z3 > kEncPreMax)
-        return fail(c, PVAC_ENOSYS, "enc_caps: noise plan beyond 256 pre-merge edges per half (depth hint > 124 with the default Params)");
+    if (plan_over(c, z2, z3)) return plan_refused(c, "enc_caps");
     const uint32_t npre = 8 + 2 * z2 + 3 * z3;
     if (layers_per_value) *layers_per_value = 2;
     if (edges_per_value) *edges_per_value = 2 * npre;
-    // mask 2 + per half: nonce 2, signal 2*8 + 2*7, salts npre, noise picks/signs/coefficients, shuffle
-    if (draws_hint) *draws_hint = 2 + 2 * (2 + 16 + 14 + npre + z2 * 5 + z3 * 10 + npre) + 64;
+    // mask 2 + per half: nonce 2, signal 2*8 + 2*7, salts npre, noise picks/signs/coefficients, shuffle,
+    // and the slack (32 per half up to 256 edges, growing with the plan above: enc_wide.hpp)
+    if (draws_hint) *draws_hint = (uint32_t)enc_draws_hint(z2, z3, c->prm.B, 2);
     return PVAC_OK;
 } catch (...) { return caught(c, "enc_caps"); }
 
@@ -207,9 +222,19 @@ int pvac_hip_enc_value_depth(pvac_hip_ctx* c, size_t n, const uint64_t* values, 
     a.n = n;
     a.canon = c->prm.canon_tag;
     a.powg = c->powg.get();
+    if (plan_over(c, a.Z2, a.Z3)) return plan_refused(c, "enc_value");
     const uint32_t npre = 8 + 2 * a.Z2 + 3 * a.Z3;
-    if ((uint64_t)8 + 2ull * a.Z2 + 3ull * a.Z3 > kEncPreMax)
-        return fail(c, PVAC_ENOSYS, "enc_value: noise plan beyond 256 pre-merge edges per half (depth hint > 124 with the default Params)");
+    if (npre > kEncPreMax) {   // VALUE items on the wide route: the same layout, value i's draws at rnd + i rnd_stride
+        std::vector<uint64_t> v(n);
+        hipError_t ev = hipMemcpyAsync(v.data(), values, n * 8, hipMemcpyDeviceToHost, c->stream);
+        if (ev == hipSuccess) ev = hipStreamSynchronize(c->stream);
+        if (ev != hipSuccess) return hip_fail(c, ev, "enc_value (values)");
+        std::vector<pvac_enc_item> items(n);
+        for (size_t i = 0; i < n; ++i)
+            items[i] = pvac_enc_item{v[i], 0, depth_hint, PVAC_ENC_ITEM_VALUE, (uint64_t)i * rnd_stride, rnd_stride};
+        const std::vector<item_plan> plans(n, item_plan{a.Z2, a.Z3, npre, 2});
+        return run_enc_items(c, n, items.data(), plans, rnd, C, flags, status);
+    }
     const uint64_t cores = (uint64_t)n * enc_cores_per_value(a.Z2, a.Z3);
     const uint64_t pe = (uint64_t)n * 2 * npre;
     const uint32_t sw = c->prm.m_bits / 64;
@@ -245,14 +270,16 @@ int pvac_hip_enc_value_depth(pvac_hip_ctx* c, size_t n, const uint64_t* values, 
     pvac_ct_batch out = *C;
     if (!with_sigma) out.sigma = nullptr;
     if (e == hipSuccess) e = launch_enc_finish(a, A, pre, out, status, c->stream);
+    if (e == hipSuccess) {   // pvac_hip_enc_path_count: n narrow items, one sub-batch, one run
+        c->prf.enc_path[0] += n;
+        ++c->prf.enc_path[2];
+        ++c->prf.enc_path[3];
+    }
     return hip_fail(c, e, "enc_value");
 } catch (...) { return caught(c, "enc_value"); }
 
 // ---------------------------------------------------------------- enc_items
 namespace {
-struct item_plan {
-    uint32_t z2, z3, npre, halves;
-};
 // kinds and plans of a batch of items; PVAC_EINVAL / PVAC_ENOSYS before anything else happens
 int plan_items(pvac_hip_ctx* c, size_t n, const pvac_enc_item* items, std::vector<item_plan>& plans, const char* who) {
     plans.resize(n);
@@ -261,8 +288,7 @@ int plan_items(pvac_hip_ctx* c, size_t n, const pvac_enc_item* items, std::vecto
             return fail(c, PVAC_EINVAL, std::string(who) + ": unknown item kind");
         item_plan& p = plans[i];
         plan_noise(c, items[i].depth_hint, p.z2, p.z3);
-        if ((uint64_t)8 + 2ull * p.z2 + 3ull * p.z3 > kEncPreMax)
-            return fail(c, PVAC_ENOSYS, std::string(who) + ": noise plan beyond 256 pre-merge edges per half (depth hint > 124 with the default Params)");
+        if (plan_over(c, p.z2, p.z3)) return plan_refused(c, who);
         p.npre = 8 + 2 * p.z2 + 3 * p.z3;
         p.halves = items[i].kind == PVAC_ENC_ITEM_VALUE ? 2 : 1;
     }
@@ -281,9 +307,9 @@ int pvac_hip_enc_items_caps(pvac_hip_ctx* c, size_t n, const pvac_enc_item* item
         const item_plan& p = plans[i];
         ls += p.halves;
         es += (uint64_t)p.halves * p.npre;
-        // per half: nonce 2, signal 2*8 + 2*7, salts npre, noise picks/signs/coefficients, shuffle; a value's mask 2
-        const uint64_t half = 2 + 16 + 14 + p.npre + p.z2 * 5ull + p.z3 * 10ull + p.npre;
-        if (draws_hint) draws_hint[i] = p.halves == 2 ? 2 + 2 * half + 64 : half + 32;
+        // per half: nonce 2, signal 2*8 + 2*7, salts npre, noise picks/signs/coefficients, shuffle; a value's mask 2;
+        // the slack is 32 per half up to 256 edges and grows with the plan above (enc_wide.hpp)
+        if (draws_hint) draws_hint[i] = enc_draws_hint(p.z2, p.z3, c->prm.B, p.halves);
     }
     if (layer_slots) *layer_slots = ls;
     if (edge_slots) *edge_slots = es;
@@ -306,6 +332,24 @@ int pvac_hip_enc_items(pvac_hip_ctx* c, size_t n, const pvac_enc_item* items, co
     for (size_t i = 0; i < n; ++i)
         if (items[i].rnd_off > rnd_words || items[i].rnd_cnt > rnd_words - items[i].rnd_off)
             return fail(c, PVAC_EINVAL, "enc_items: an item's draw range lies outside rnd_words");
+    uint64_t halves = 0, pe = 0;
+    for (size_t i = 0; i < n; ++i) {
+        halves += plans[i].halves;
+        pe += (uint64_t)plans[i].halves * plans[i].npre;
+    }
+    if (halves > layer_cap || pe > edge_cap)
+        return fail(c, PVAC_ENOMEM, "enc_items: layer_cap / edge_cap below pvac_hip_enc_items_caps");
+    C->n = n;
+    if (!n) return PVAC_OK;
+    return run_enc_items(c, n, items, plans, rnd, C, flags, status);
+} catch (...) { return caught(c, "enc_items"); }
+
+}  // extern "C"
+
+namespace {
+// A call of narrow items within the budget: one sub-batch, the launches of k_enc_items.hip alone
+int run_enc_items_narrow(pvac_hip_ctx* c, size_t n, const pvac_enc_item* items, const std::vector<item_plan>& plans,
+                         const uint64_t* rnd, pvac_ct_batch* C, bool with_sigma, uint32_t* status) {
     // one host image: records | work list | permutation (uploaded in one copy)
     std::vector<enc_item_rec> recs(n);
     std::vector<uint64_t> work;
@@ -329,17 +373,13 @@ int pvac_hip_enc_items(pvac_hip_ctx* c, size_t n, const pvac_enc_item* items, co
         pe += (uint64_t)p.halves * p.npre;
         cores += (uint64_t)p.halves * 3 * std::max(p.z2 + p.z3, 1u);
     }
-    if (halves > layer_cap || pe > edge_cap)
-        return fail(c, PVAC_ENOMEM, "enc_items: layer_cap / edge_cap below pvac_hip_enc_items_caps");
-    C->n = n;
-    if (!n) return PVAC_OK;
     std::vector<uint32_t> perm(n);
     for (size_t i = 0; i < n; ++i) perm[i] = (uint32_t)i;
     std::stable_sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) {
         return (uint64_t)plans[x].npre * plans[x].halves > (uint64_t)plans[y].npre * plans[y].halves;
     });
     prf_consts k{};
-    rc = prf_setup(c, k);
+    int rc = prf_setup(c, k);
     if (rc) return rc;
     const uint32_t sw = c->prm.m_bits / 64;
     // arena: records | work | perm | headers | requests | cores | pre CSR (4 x n) | pre layers |
@@ -412,7 +452,228 @@ int pvac_hip_enc_items(pvac_hip_ctx* c, size_t n, const pvac_enc_item* items, co
     if (!with_sigma) out.sigma = nullptr;
     if (e == hipSuccess) e = timed("enc_items_finish", [&] { return launch_enc_items_finish(a, pre, out, status, c->stream); });
     return hip_fail(c, e, "enc_items");
-} catch (...) { return caught(c, "enc_items"); }
+}
+
+// One sub-batch [i0, i1) of a call on the mixed path: the narrow items through k_enc_items.hip over a
+// compact record list (their index entries and status land in scratch and are scattered to their
+// places), the wide items through k_enc_wide.hip. Items, halves and pre-edge slots are numbered from
+// the sub-batch's first; base_l / base_e are its first layer and edge slot in C.
+int run_enc_sub(pvac_hip_ctx* c, const prf_consts& k, const pvac_enc_item* items, const std::vector<item_plan>& plans, size_t i0,
+                size_t i1, uint64_t base_l, uint64_t base_e, const uint64_t* rnd, pvac_ct_batch* C, bool with_sigma, bool wide_all,
+                uint32_t* status) {
+    const uint32_t B = c->prm.B, sw = c->prm.m_bits / 64;
+    std::vector<enc_item_rec> rn, rw;
+    std::vector<uint32_t> nid, wid, half_item;
+    std::vector<uint64_t> work_n, work_w, fin;
+    uint64_t halves = 0, pe = 0, cores = 0;
+    for (size_t i = i0; i < i1; ++i) {
+        const item_plan& p = plans[i];
+        const bool wide = wide_all || p.npre > kEncPreMax;
+        enc_item_rec r{};
+        r.v_lo = items[i].v_lo;
+        r.v_hi = items[i].v_hi;
+        r.rnd_off = items[i].rnd_off;
+        r.rnd_cnt = (uint32_t)std::min<uint64_t>(items[i].rnd_cnt, 0xFFFFFFFFull);
+        r.Z2 = p.z2;
+        r.Z3 = p.z3;
+        r.halves = p.halves;
+        r.half_off = halves;
+        r.pre_off = pe;
+        r.req_off = cores;
+        (wide ? rw : rn).push_back(r);
+        (wide ? wid : nid).push_back((uint32_t)(i - i0));
+        for (uint32_t h = 0; h < p.halves; ++h) {
+            half_item.push_back((uint32_t)(i - i0) << 1 | h);
+            for (uint32_t g = 0; g <= p.z2 + p.z3; ++g)
+                if (wide) work_w.push_back((halves + h) << 32 | g);
+                else work_n.push_back((halves + h) << 16 | g);
+            if (wide)   // a half merges down to at most 2 B edges
+                for (uint32_t s0 = 0; s0 < std::min<uint64_t>(p.npre, 2ull * B); s0 += kEncWideFinChunk)
+                    fin.push_back((halves + h) << 32 | s0);
+        }
+        halves += p.halves;
+        pe += (uint64_t)p.halves * p.npre;
+        cores += (uint64_t)p.halves * 3 * std::max(p.z2 + p.z3, 1u);
+    }
+    const uint64_t nn = rn.size(), nw = rw.size();
+    std::vector<uint32_t> perm(nn);   // the narrow plan kernel's order: largest plan first
+    for (size_t t = 0; t < nn; ++t) perm[t] = (uint32_t)t;
+    std::stable_sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) {
+        return (uint64_t)(8 + 2 * rn[x].Z2 + 3 * rn[x].Z3) * rn[x].halves > (uint64_t)(8 + 2 * rn[y].Z2 + 3 * rn[y].Z3) * rn[y].halves;
+    });
+    enc_sub_shape sh;
+    sh.n = i1 - i0;
+    sh.n_narrow = nn;
+    sh.n_wide = nw;
+    sh.halves = halves;
+    sh.pe = pe;
+    sh.cores = cores;
+    sh.work_narrow = work_n.size();
+    sh.work_wide = work_w.size();
+    sh.fin = fin.size();
+    sh.B = B;
+    sh.sigma_words = with_sigma ? sw : 0;
+    const enc_sub_layout L = enc_sub_layout_of(sh, sizeof(enc_item_rec), sizeof(enc_half_hdr), prf_request_bytes(), sizeof(pvac_layer));
+    if (const hipError_t ea = c->prf.enc_arena.grow(L.total, L.total)) return hip_fail(c, ea, "alloc enc scratch");
+    uint8_t* A = c->prf.enc_arena.get();
+    std::vector<uint8_t> img(L.up_bytes, 0);
+    auto put = [&](uint64_t off, const void* p, size_t bytes) { if (bytes) std::memcpy(img.data() + off, p, bytes); };
+    put(L.recs_narrow, rn.data(), nn * sizeof(enc_item_rec));
+    put(L.recs_wide, rw.data(), nw * sizeof(enc_item_rec));
+    put(L.nid, nid.data(), nn * 4);
+    put(L.wid, wid.data(), nw * 4);
+    put(L.perm, perm.data(), nn * 4);
+    put(L.work_narrow, work_n.data(), work_n.size() * 8);
+    put(L.work_wide, work_w.data(), work_w.size() * 8);
+    put(L.fin, fin.data(), fin.size() * 8);
+    put(L.half_item, half_item.data(), half_item.size() * 4);
+    if (const hipError_t eu = upload_words(c, A, img.data(), L.up_bytes)) return hip_fail(c, eu, "enc_items (upload)");
+    // the pre-merge batch: the narrow items' index entries first, then the wide items'
+    pvac_ct_batch pre{};
+    pre.n = sh.n;
+    pre.l_off = (uint64_t*)(A + L.pre_idx);
+    pre.l_cnt = pre.l_off + sh.n;
+    pre.e_off = pre.l_cnt + sh.n;
+    pre.e_cnt = pre.e_off + sh.n;
+    pre.layers = (pvac_layer*)(A + L.lay);
+    pre.meta = (uint64_t*)(A + L.e);
+    pre.w_lo = pre.meta + pe;
+    pre.w_hi = pre.w_lo + pe;
+    pre.sigma = with_sigma ? (uint64_t*)(A + L.sig) : nullptr;
+    pre.sigma_words = with_sigma ? sw : 0;
+    enc_items_args a{};
+    a.n = nn;
+    a.n_work = work_n.size();
+    a.n_halves = halves;
+    a.recs = (const enc_item_rec*)(A + L.recs_narrow);
+    a.work = (const uint64_t*)(A + L.work_narrow);
+    a.perm = (const uint32_t*)(A + L.perm);
+    a.rnd = rnd;
+    a.powg = c->powg.get();
+    a.canon = c->prm.canon_tag;
+    a.B = B;
+    a.hdr = (enc_half_hdr*)(A + L.hdr);
+    a.salt = pre.w_hi + pe;
+    a.rlo = a.salt + pe;
+    a.rhi = a.rlo + pe;
+    a.key = (uint32_t*)(A + L.key);
+    a.grp = A + L.grp;
+    a.slot = a.grp + pe;
+    enc_wide_args w{};
+    w.n = nw;
+    w.n_work = work_w.size();
+    w.n_fin = fin.size();
+    w.recs = (const enc_item_rec*)(A + L.recs_wide);
+    w.item = (const uint32_t*)(A + L.wid);
+    w.work = (const uint64_t*)(A + L.work_wide);
+    w.fin = (const uint64_t*)(A + L.fin);
+    w.half_item = (const uint32_t*)(A + L.half_item);
+    w.rnd = rnd;
+    w.powg = a.powg;
+    w.canon = a.canon;
+    w.base_l = base_l;
+    w.base_e = base_e;
+    w.B = B;
+    w.pre_base = (uint32_t)nn;
+    w.hdr = a.hdr;
+    w.key = a.key;
+    w.salt = a.salt;
+    w.rlo = a.rlo;
+    w.rhi = a.rhi;
+    w.occ = (uint32_t*)(A + L.occ);
+    w.ord = w.occ + pe;
+    w.gstart = w.ord + pe;
+    w.slot = w.gstart + pe;
+    w.tab = (uint32_t*)(A + L.tab);
+    w.dlast = (uint64_t*)(A + L.dlast);
+    // C as the sub-batch sees it: index arrays and status from its first item, rows from its first slot
+    pvac_ct_batch out = *C;
+    out.l_off += i0;
+    out.l_cnt += i0;
+    out.e_off += i0;
+    out.e_cnt += i0;
+    out.layers += base_l;
+    out.meta += base_e;
+    out.w_lo += base_e;
+    out.w_hi += base_e;
+    out.sigma = with_sigma ? C->sigma + base_e * C->sigma_words : nullptr;
+    uint32_t* st = status + i0;
+    pvac_ct_batch tmp = out;   // the narrow kernels' index entries, compact
+    tmp.l_off = (uint64_t*)(A + L.tmp_idx);
+    tmp.l_cnt = tmp.l_off + nn;
+    tmp.e_off = tmp.l_cnt + nn;
+    tmp.e_cnt = tmp.e_off + nn;
+    uint32_t* tmp_st = (uint32_t*)(A + L.tmp_status);
+    prf_request* req = (prf_request*)(A + L.req);
+    uint64_t* core = (uint64_t*)(A + L.core);
+    auto timed = [&](const char* name, auto&& launch) {
+        scoped_timer tk(c, name);
+        return launch();
+    };
+    hipError_t e = hipSuccess;
+    if (nw) e = hipMemsetAsync(w.tab, 0, nw * 2 * 2 * (uint64_t)B * 4, c->stream);
+    if (e == hipSuccess && nn) e = timed("enc_items_plan", [&] { return launch_enc_items_plan(a, req, pre, tmp_st, c->stream); });
+    if (e == hipSuccess && nw) e = timed("enc_items_plan_wide", [&] { return launch_enc_wide_replay(w, req, pre, out, st, c->stream); });
+    if (e == hipSuccess) e = timed("enc_items_prf", [&] { return launch_prf_cores(k, req, cores, core, c->stream); });
+    if (e == hipSuccess && nw) e = timed("enc_items_order_wide", [&] { return launch_enc_wide_order(w, c->stream); });
+    if (e == hipSuccess && nn) e = timed("enc_items_weights", [&] { return launch_enc_items_weights(a, core, pre, c->stream); });
+    if (e == hipSuccess && nw) e = timed("enc_items_weights_wide", [&] { return launch_enc_wide_weights(w, core, pre, c->stream); });
+    if (e == hipSuccess && with_sigma)
+        e = timed("enc_items_sigma", [&] { return launch_sigma(c->H, c->prm, pre, a.salt, nullptr, c->num_cus, c->stream); });
+    if (e == hipSuccess && nn)
+        e = timed("enc_items_finish", [&] {
+            const hipError_t ef = launch_enc_items_finish(a, pre, tmp, tmp_st, c->stream);
+            return ef != hipSuccess ? ef : launch_enc_scatter_index(nn, (const uint32_t*)(A + L.nid), tmp, tmp_st, base_l, base_e, out, st, c->stream);
+        });
+    if (e == hipSuccess && nw) e = timed("enc_items_finish_wide", [&] { return launch_enc_wide_finish(w, pre, out, st, c->stream); });
+    if (e == hipSuccess) {
+        c->prf.enc_path[0] += nn;
+        c->prf.enc_path[1] += nw;
+        ++c->prf.enc_path[2];
+    }
+    return hip_fail(c, e, "enc_items");
+}
+
+int run_enc_items(pvac_hip_ctx* c, size_t n, const pvac_enc_item* items, const std::vector<item_plan>& plans, const uint64_t* rnd,
+                  pvac_ct_batch* C, uint32_t flags, uint32_t* status) {
+    const bool with_sigma = (flags & PVAC_ENC_WITH_SIGMA) != 0, wide_all = (flags & PVAC_ENC_WIDE_ALL) != 0;
+    C->n = n;
+    if (!n) return PVAC_OK;
+    std::vector<uint64_t> item_pe(n);
+    bool any_wide = wide_all;
+    for (size_t i = 0; i < n; ++i) {
+        item_pe[i] = (uint64_t)plans[i].halves * plans[i].npre;
+        any_wide |= plans[i].npre > kEncPreMax;
+    }
+    std::vector<size_t> cuts;
+    enc_cuts(item_pe.data(), n, c->prf.enc_budget, cuts);
+    ++c->prf.enc_path[3];
+    if (!any_wide && cuts.size() == 2) {
+        const int rc = run_enc_items_narrow(c, n, items, plans, rnd, C, with_sigma, status);
+        if (!rc) {
+            c->prf.enc_path[0] += n;
+            ++c->prf.enc_path[2];
+        }
+        return rc;
+    }
+    prf_consts k{};
+    int rc = prf_setup(c, k);
+    if (rc) return rc;
+    scoped_timer t(c, "enc_items");
+    uint64_t base_l = 0, base_e = 0;
+    for (size_t s = 0; s + 1 < cuts.size(); ++s) {
+        rc = run_enc_sub(c, k, items, plans, cuts[s], cuts[s + 1], base_l, base_e, rnd, C, with_sigma, wide_all, status);
+        if (rc) return rc;
+        for (size_t i = cuts[s]; i < cuts[s + 1]; ++i) {
+            base_l += plans[i].halves;
+            base_e += item_pe[i];
+        }
+    }
+    return PVAC_OK;
+}
+}  // namespace
+
+extern "C" {
 
 int pvac_hip_base_R(pvac_hip_ctx* c, const pvac_ct_batch* X, uint64_t* R_out) try {
     if (!c || !batch_ok(X) || (X->n && !R_out)) return fail(c, PVAC_EINVAL, "base_R: arguments");
