@@ -129,6 +129,48 @@ __device__ __forceinline__ void fp_mul_fold1(const fp& a, const fp& b, uint64_t&
     x1 = join32(w2, w3);
 }
 
+// fp_mul_fold1 with the first word of rows 1..3 added through the multiply's 64-bit addend:
+// A[i] B[0] + z[i] <= (2^32 - 1)^2 + 2^32 - 1 < 2^64, so z[i] rides in as the addend and the row's
+// carry chain starts one word later (one add_co less per row, one more register move).
+__device__ __forceinline__ void fp_mul_fold1f(const fp& a, const fp& b, uint64_t& x0, uint64_t& x1) {
+    const uint32_t A[4] = {lo32(a.lo), hi32(a.lo), lo32(a.hi), hi32(a.hi)};
+    const uint32_t B[4] = {lo32(b.lo), hi32(b.lo), lo32(b.hi), hi32(b.hi)};
+    uint32_t z[8];
+    {
+        uint64_t t = (uint64_t)A[0] * B[0];
+        z[0] = lo32(t);
+#pragma unroll
+        for (int j = 1; j < 4; ++j) {
+            t = (uint64_t)A[0] * B[j] + (t >> 32);
+            z[j] = lo32(t);
+        }
+        z[4] = hi32(t);
+    }
+#pragma unroll
+    for (int i = 1; i < 4; ++i) {
+        uint32_t r[5];
+        uint64_t t = (uint64_t)A[i] * B[0] + z[i];   // < 2^64 (above)
+        z[i] = lo32(t);
+#pragma unroll
+        for (int j = 1; j < 4; ++j) {
+            t = (uint64_t)A[i] * B[j] + (t >> 32);   // (2^32 - 1)^2 + 2^32 - 1 < 2^64
+            r[j] = lo32(t);
+        }
+        r[4] = hi32(t);
+        uint32_t c = 0;
+#pragma unroll
+        for (int j = 1; j < 4; ++j) z[i + j] = addc(z[i + j], r[j], c, c);
+        z[i + 4] = r[4] + c;   // the partial product fits in i + 5 words: no carry out
+    }
+    uint32_t c = 0;
+    const uint32_t w0 = addc(z[0], funnel(z[4], z[3], 31), 0u, c);
+    const uint32_t w1 = addc(z[1], funnel(z[5], z[4], 31), c, c);
+    const uint32_t w2 = addc(z[2], funnel(z[6], z[5], 31), c, c);
+    const uint32_t w3 = (z[3] & 0x7FFFFFFFu) + funnel(z[7], z[6], 31) + c;
+    x0 = join32(w0, w1);
+    x1 = join32(w2, w3);
+}
+
 // 128-bit x -> 43/43/42-bit limbs; up to 2^21 of them sum in u64 limbs without overflow
 __device__ __forceinline__ void fp_split3_128(uint64_t x0, uint64_t x1, uint64_t& l0, uint64_t& l1, uint64_t& l2) {
     const uint32_t w0 = lo32(x0), w1 = hi32(x0), w2 = lo32(x1), w3 = hi32(x1);
@@ -248,6 +290,50 @@ __device__ __forceinline__ fp fp_fold3_44(uint64_t l0, uint64_t l1, uint64_t l2)
     uint32_t x2 = addc(v2, 0u, c, c);
     uint32_t x3 = (v3 & 0x7FFFFFFFu) + c;
     // x >= 2^127 -> (x - 2^127) + 1 (< 2^14: no carry); x == p -> 0
+    const uint32_t t = x3 >> 31;
+    x3 &= 0x7FFFFFFFu;
+    x0 += t;
+    const uint32_t keep = ((x3 == 0x7FFFFFFFu) & ((x0 & x1 & x2) == 0xFFFFFFFFu)) ? 0u : ~0u;
+    x0 &= keep; x1 &= keep; x2 &= keep; x3 &= keep;
+    return fp{join32(x0, x1), join32(x2, x3)};
+}
+
+// 128-bit x -> 48/48/32-bit limbs on byte-aligned cuts: l0 = bits 0..47, l1 = bits 48..95,
+// l2 = bits 96..127 (word 3 as it is, under a zero high word). One mask, one funnel and one
+// shift, against two funnels, two shift-and-masks and a shift for the 44/44/40 cuts.
+// Capacity: up to 4096 of them sum into u64 limbs of < 2^60, < 2^60 and < 2^44, so bits 52..63 of
+// the third limb stay free (k_ct_mul_fresh3 keeps the emit cell id there).
+constexpr uint32_t kLimb48MaxAddends = 4096;
+static_assert((uint64_t)kLimb48MaxAddends << 48 <= 1ull << 60 && (uint64_t)kLimb48MaxAddends << 32 <= 1ull << 52,
+              "48/48/32-bit limbs: 48-bit limbs stay below 2^60, the 32-bit limb below bit 52");
+__device__ __forceinline__ void fp_split3_48(uint64_t x0, uint64_t x1, uint64_t& l0, uint64_t& l1, uint64_t& l2) {
+    const uint32_t w0 = lo32(x0), w1 = hi32(x0), w3 = hi32(x1);
+    uint32_t w2 = lo32(x1);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(w2));   // w2 >> 16 stays one 32-bit shift (seen through, it becomes a 64-bit shift and a mask)
+#endif
+    l0 = join32(w0, w1 & 0xFFFFu);                   // bits 0..47
+    l1 = join32(funnel(w2, w1, 16), w2 >> 16);       // bits 48..95
+    l2 = join32(w3, 0u);                             // bits 96..127
+}
+
+// (l0 + l1 * 2^48 + l2 * 2^96) mod p, canonical (p itself maps to 0), for l0, l1 < 2^60 and
+// l2 < 2^44
+__device__ __forceinline__ fp fp_fold3_48(uint64_t l0, uint64_t l1, uint64_t l2) {
+    // V < 2^141 as five words; l2 lands on words 3 and 4 unshifted
+    uint32_t c = 0;
+    const uint32_t v0 = lo32(l0);
+    const uint32_t v1 = addc(hi32(l0), lo32(l1) << 16, 0u, c);
+    const uint32_t v2 = addc(funnel(hi32(l1), lo32(l1), 16), 0u, c, c);   // bits 16..47 of l1
+    const uint32_t v3 = addc(hi32(l1) >> 16, lo32(l2), c, c);             // < 2^12 + < 2^32
+    const uint32_t v4 = hi32(l2) + c;                                      // < 2^12 + 1
+    // x = (V mod 2^127) + (V >> 127) < 2^127 + 2^14
+    const uint32_t top = funnel(v4, v3, 31);
+    uint32_t x0 = addc(v0, top, 0u, c);
+    uint32_t x1 = addc(v1, 0u, c, c);
+    uint32_t x2 = addc(v2, 0u, c, c);
+    uint32_t x3 = (v3 & 0x7FFFFFFFu) + c;
+    // x >= 2^127 -> (x - 2^127) + 1 (< 2^14 + 1: no carry); x == p -> 0
     const uint32_t t = x3 >> 31;
     x3 &= 0x7FFFFFFFu;
     x0 += t;

@@ -19,7 +19,7 @@
 //                        so no SHA work sits on the aggregation kernel's critical path.
 //   k_ct_mul_fresh3    : one 512-thread workgroup per pair, persistent over the batch, <= 53 KB
 //                        LDS (three workgroups per CU). Emit positions are computed before the
-//                        products; sums are exact (44/44/40-bit limbs added with ds_add_u64,
+//                        products; sums are exact (48/48/32-bit limbs added with ds_add_u64,
 //                        order independent). compact_layers is a wave-wide bitmask closure over
 //                        LDS-resident parent masks. See the phase list above the kernel.
 #include <atomic>
@@ -314,8 +314,8 @@ __device__ __forceinline__ void stage_pair(const fresh_pref& f, const fresh_hdr&
 //                  compact_layers
 //   P4 positions : each emitting cell gets its hash-order emit position p (segment offset added
 //                  from the segment totals); p goes into the cell word, the cell id into limb 2 of p
-//   P5 products  : fp_mul of every product, 44/44/40-bit limbs added into position p's
-//                  accumulators (3 ds_add_u64)
+//   P5 products  : fp_mul of every product, 48/48/32-bit limbs (fp_split3_48: byte-aligned cuts)
+//                  added into position p's accumulators (3 ds_add_u64)
 //   P6 writer    : positions p = tid, tid + 448, ... fold their limbs (coalesced LDS reads), write
 //                  the edge records coalesced, clear. A folded sum of 0 (a cancelling key, or a
 //                  zero weight) means the optimistic emit in P2 was wrong, and guard_budget /
@@ -413,6 +413,9 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
     constexpr uint32_t kT16 = 0xFFFFu;                   // no first-insert time
     static_assert(BS % 64 == 0 && BS >= (int)kFreshEdgesMax && NW <= 16 && U % 2 == 0, "fresh geometry");
     static_assert(kFreshProdMax <= 16u * 256u, "16 scan segments of 256 product times");
+    // a position takes at most every product of the pair: limbs 0 and 1 stay below 2^60, limb 2 below
+    // 2^44, so the cell id P4 writes at bit 52 of limb 2 survives the sums (fp_split3_48)
+    static_assert(kFreshProdMax <= kLimb48MaxAddends, "48/48/32-bit limb sums: at most 4096 addends per position");
     argp gq = launder((uint64_t)gp);
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     uint32_t* tkey = (uint32_t*)(lds + Ls.tkey);
@@ -995,8 +998,8 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
             const uint32_t tid = prod_id();
             auto accumulate = [&](const ulonglong2& x, const ulonglong2& y, uint32_t p) {
                 uint64_t x0, x1, l0, l1, l2;
-                fp_mul_fold1(fp{x.x, x.y}, fp{y.x, y.y}, x0, x1);
-                fp_split3_44(x0, x1, l0, l1, l2);
+                fp_mul_fold1f(fp{x.x, x.y}, fp{y.x, y.y}, x0, x1);
+                fp_split3_48(x0, x1, l0, l1, l2);
                 unsigned long long* q = lim + 3u * p;
                 atomicAdd(q, (unsigned long long)l0);
                 atomicAdd(q + 1, (unsigned long long)l1);
@@ -1039,6 +1042,7 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
         //      the coalesced writer over emit positions (not the control wave: its vector-memory
         //      queue stays free of stores), then clear the cell words
         stage_pair(pf, nxt, Bm, a_w, a_inf, b_w, b_inf, pm, misc, stage_id());
+        M3(6);
         {
             const uint32_t tid = opaque(threadIdx.x);
             uint64_t* cm = gq->C.meta + ceo;
@@ -1062,17 +1066,21 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
                 q[0] = z64;
                 q[1] = z64;
                 q[2] = z64;
-                const uint32_t cell = (uint32_t)(l2c >> 52);
-                const fp w = fp_fold3_44(l0, l1, l2c & ((1ull << 52) - 1ull));
+                // the cell id from limb 2's high dword alone (32-bit shifts): slot at bits 21..31,
+                // channel at bit 20
+                const uint32_t h2 = hi32(l2c);
+                const fp w = fp_fold3_48(l0, l1, l2c & ((1ull << 52) - 1ull));
                 zmask |= __builtin_amdgcn_ballot_w64(!fp_nonzero(w));
-                const uint32_t s = cell >> 1;
+                const uint32_t s = h2 >> 21;
                 const uint32_t lp = __umulhi(s, bdiv);
                 const uint32_t r = s - lp * Bm;
                 const uint32_t lid = ident ? base + lp : remap[base + lp];
+                // make_meta(lid, r, channel): r < B <= kFreshKeysMax < 2^16, the channel bit moves
+                // from bit 20 to bit 16 of the high word
+                const uint32_t mh = r | ((h2 >> 4) & 0x10000u);
                 // streaming stores: the output is not read again by this kernel (-1%, A/B)
-                const uint64_t mv = make_meta(lid, r, cell & 1u);
                 const uint32_t bo = p * 8u;   // < 2^31: a pair has <= 2 x 4096 edges
-                __builtin_amdgcn_raw_buffer_store_b64(u2v{(uint32_t)mv, (uint32_t)(mv >> 32)}, rm, bo, 0, 2);
+                __builtin_amdgcn_raw_buffer_store_b64(u2v{lid, mh}, rm, bo, 0, 2);
                 __builtin_amdgcn_raw_buffer_store_b64(u2v{(uint32_t)w.lo, (uint32_t)(w.lo >> 32)}, rl, bo, 0, 2);
                 __builtin_amdgcn_raw_buffer_store_b64(u2v{(uint32_t)w.hi, (uint32_t)(w.hi >> 32)}, rh, bo, 0, 2);
                 if (sp) sp[p] = p;   // hash order == emit order here
