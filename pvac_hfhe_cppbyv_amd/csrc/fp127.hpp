@@ -317,9 +317,13 @@ __device__ __forceinline__ void fp_split3_48(uint64_t x0, uint64_t x1, uint64_t&
     l2 = join32(w3, 0u);                             // bits 96..127
 }
 
-// (l0 + l1 * 2^48 + l2 * 2^96) mod p, canonical (p itself maps to 0), for l0, l1 < 2^60 and
-// l2 < 2^44
-__device__ __forceinline__ fp fp_fold3_48(uint64_t l0, uint64_t l1, uint64_t l2) {
+// The fold of fp_fold3_48 without its canonical finish: the four words of an x < 2^127 with
+// x == l0 + l1 * 2^48 + l2 * 2^96 (mod p), for l0, l1 < 2^60 and l2 < 2^44. x is canonical
+// except that p itself is not mapped to 0 (fp_fold3_48_finish does that). x is a multiple of p
+// only as 0 or p, so x[3] == 0 || x[3] == 0x7FFFFFFF (fp_fold3_48_rare) is necessary for the
+// canonical value to be 0 and for the finish to change anything: a caller that tests it may skip
+// the finish, and its zero test, everywhere else.
+__device__ __forceinline__ void fp_fold3_48_words(uint64_t l0, uint64_t l1, uint64_t l2, uint32_t (&x)[4]) {
     // V < 2^141 as five words; l2 lands on words 3 and 4 unshifted
     uint32_t c = 0;
     const uint32_t v0 = lo32(l0);
@@ -329,17 +333,28 @@ __device__ __forceinline__ fp fp_fold3_48(uint64_t l0, uint64_t l1, uint64_t l2)
     const uint32_t v4 = hi32(l2) + c;                                      // < 2^12 + 1
     // x = (V mod 2^127) + (V >> 127) < 2^127 + 2^14
     const uint32_t top = funnel(v4, v3, 31);
-    uint32_t x0 = addc(v0, top, 0u, c);
-    uint32_t x1 = addc(v1, 0u, c, c);
-    uint32_t x2 = addc(v2, 0u, c, c);
-    uint32_t x3 = (v3 & 0x7FFFFFFFu) + c;
-    // x >= 2^127 -> (x - 2^127) + 1 (< 2^14 + 1: no carry); x == p -> 0
-    const uint32_t t = x3 >> 31;
-    x3 &= 0x7FFFFFFFu;
-    x0 += t;
-    const uint32_t keep = ((x3 == 0x7FFFFFFFu) & ((x0 & x1 & x2) == 0xFFFFFFFFu)) ? 0u : ~0u;
-    x0 &= keep; x1 &= keep; x2 &= keep; x3 &= keep;
-    return fp{join32(x0, x1), join32(x2, x3)};
+    x[0] = addc(v0, top, 0u, c);
+    x[1] = addc(v1, 0u, c, c);
+    x[2] = addc(v2, 0u, c, c);
+    x[3] = (v3 & 0x7FFFFFFFu) + c;
+    // x >= 2^127 -> (x - 2^127) + 1 (< 2^14 + 1: no carry)
+    const uint32_t t = x[3] >> 31;
+    x[3] &= 0x7FFFFFFFu;
+    x[0] += t;
+}
+__device__ __forceinline__ bool fp_fold3_48_rare(const uint32_t (&x)[4]) { return x[3] == 0x7FFFFFFFu || x[3] == 0u; }
+// x == p -> 0 (x < 2^127 from fp_fold3_48_words)
+__device__ __forceinline__ fp fp_fold3_48_finish(const uint32_t (&x)[4]) {
+    const uint32_t keep = ((x[3] == 0x7FFFFFFFu) & ((x[0] & x[1] & x[2]) == 0xFFFFFFFFu)) ? 0u : ~0u;
+    return fp{join32(x[0] & keep, x[1] & keep), join32(x[2] & keep, x[3] & keep)};
+}
+
+// (l0 + l1 * 2^48 + l2 * 2^96) mod p, canonical (p itself maps to 0), for l0, l1 < 2^60 and
+// l2 < 2^44: fold + finish
+__device__ __forceinline__ fp fp_fold3_48(uint64_t l0, uint64_t l1, uint64_t l2) {
+    uint32_t x[4];
+    fp_fold3_48_words(l0, l1, l2, x);
+    return fp_fold3_48_finish(x);
 }
 
 // ---- lazy register accumulators ---------------------------------------------------------

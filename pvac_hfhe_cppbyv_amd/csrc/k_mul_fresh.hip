@@ -304,7 +304,10 @@ __device__ __forceinline__ void stage_pair(const fresh_pref& f, const fresh_hdr&
 // ================================================================ k_ct_mul_fresh3
 // Positions before products. Three workgroups per CU (<= 53 KB LDS, <= 80 VGPRs):
 //   P1 key times : every product t = i|B.E| + j lands in cell 2 s + ch (s = key slot, ch = P/M);
-//                  one ds_min_u32 per product gives each cell's first-insert time (no multiply)
+//                  one ds_min_u32 per product gives each cell's first-insert time (no multiply).
+//                  A wave classifies its product rounds in SALU (full, empty, partial): without a
+//                  partial round it runs its full rounds unclamped and unmasked and keeps their
+//                  products in registers for P5; with one it runs the clamped, masked loop
 //   P2 order     : slot owners read their two cells and the cells of their bucket's other slots:
 //                  key time, bucket first-insert time, rank in the bucket, bucket edge count
 //                  G[t_bkt]. A cell with products is assumed to emit (its sum is != 0).
@@ -315,9 +318,12 @@ __device__ __forceinline__ void stage_pair(const fresh_pref& f, const fresh_hdr&
 //   P4 positions : each emitting cell gets its hash-order emit position p (segment offset added
 //                  from the segment totals); p goes into the cell word, the cell id into limb 2 of p
 //   P5 products  : fp_mul of every product, 48/48/32-bit limbs (fp_split3_48: byte-aligned cuts)
-//                  added into position p's accumulators (3 ds_add_u64)
+//                  added into position p's accumulators (3 ds_add_u64); P1's full rounds from
+//                  registers with every lane on, the rest recomputed in the masked loop
 //   P6 writer    : positions p = tid, tid + 448, ... fold their limbs (coalesced LDS reads), write
-//                  the edge records coalesced, clear. A folded sum of 0 (a cancelling key, or a
+//                  the edge records coalesced, clear. The canonical finish (p -> 0) and the zero
+//                  test run only in a position round where a lane's top word is 0 or 0x7FFFFFFF
+//                  (wave-uniform gate). A folded sum of 0 (a cancelling key, or a
 //                  zero weight) means the optimistic emit in P2 was wrong, and guard_budget /
 //                  ORDER_CANONICAL want another order: such pairs are flagged (pair_status 3,
 //                  redo list) and the host re-runs them on the general path.
@@ -681,29 +687,63 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
             return ((((sum >> 12) & 0xFFFu) + r) << 1) | ((sum >> 24) & 1u);
         };
         M3(1);
-        // ---- P1: first-insert time of every cell. The first pass's products stay in registers
-        //      for P5: i | j << 8 | cell << 16 (i, j < 256, cell < 4096); t >= n: ~0
+        // Round classes. Product round u of a wave holds the times w0 + u BS .. w0 + u BS + 63, w0
+        // being the wave's first prod_id (prod_id is the thread id rotated by whole waves, so lane 0
+        // holds it). A round is full (all 64 times below n), empty (none) or partial: a function of
+        // n, w0 and u alone, computed in SALU. A wave without a partial round among its first U
+        // (every wave at 1,600 products) runs its `full` full rounds with no clamp, no t < n test
+        // and no mask, and nothing for the empty ones. A wave with a partial round keeps no
+        // products in registers: it runs the clamped and masked loops for n > U BS from its first
+        // product on (full = 0), in P1 and in P5.
+        auto full_rounds = [&](uint32_t w0) {
+            const uint32_t ns = __builtin_amdgcn_readfirstlane(n);
+            const uint32_t left = ns > w0 ? ns - w0 : 0u;     // products from this wave's first on
+            const uint32_t rounds = (left + BS - 1u) / BS;    // rounds with a product
+            const bool part = left + BS - rounds * BS < 64u;  // the last of them holds fewer than 64
+            return rounds > (uint32_t)U ? (uint32_t)U : part ? 0u : rounds;
+        };
+        // ---- P1: first-insert time of every cell. The products of the full rounds stay in
+        //      registers for P5: i | j << 8 | cell << 16 (i, j < 256, cell < 4096)
         uint32_t prod[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) prod[u] = ~0u;
         {
             const uint32_t tid = prod_id();
-            for (uint32_t t0 = tid; t0 < n; t0 += U * BS) {
-                uint32_t sum[U], ij[U];
+            const uint32_t full = full_rounds(__builtin_amdgcn_readfirstlane(tid));
+#pragma unroll
+            for (int u0 = 0; u0 < U; u0 += 2) {   // two rounds at a time
+                if ((uint32_t)u0 >= full) break;
+                uint32_t sum[2];
+#pragma unroll
+                for (int v = 0; v < 2; ++v) {
+                    if ((uint32_t)(u0 + v) >= full) break;
+                    const uint32_t t = tid + (uint32_t)(u0 + v) * BS;
+                    const uint32_t i = __umulhi(t << 8, mdiv);
+                    const uint32_t j = t - i * nB;
+                    prod[u0 + v] = i | (j << 8);
+                    sum[v] = a_inf[i] + b_inf[j];
+                }
+#pragma unroll
+                for (int v = 0; v < 2; ++v) {
+                    if ((uint32_t)(u0 + v) >= full) break;
+                    const uint32_t c = cell_of(sum[v]);
+                    atomicMin(&tkey[c], tid + (uint32_t)(u0 + v) * BS);
+                    prod[u0 + v] |= c << 16;
+                }
+            }
+            M3(10);
+            // further passes (n > U * BS), and every product of a wave with a partial round
+            for (uint32_t t0 = tid + (full ? U * BS : 0u); t0 < n; t0 += U * BS) {
+                uint32_t sum[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const uint32_t t = min(t0 + (uint32_t)u * BS, n - 1u);
                     const uint32_t i = __umulhi(t << 8, mdiv);
                     const uint32_t j = t - i * nB;
-                    ij[u] = i | (j << 8);
                     sum[u] = a_inf[i] + b_inf[j];
                 }
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const uint32_t t = t0 + (uint32_t)u * BS;
-                    const uint32_t c = cell_of(sum[u]);
-                    if (t < n) atomicMin(&tkey[c], t);
-                    if (t0 == tid) prod[u] = t < n ? ij[u] | (c << 16) : ~0u;
+                    if (t < n) atomicMin(&tkey[cell_of(sum[u])], t);
                 }
             }
         }
@@ -806,8 +846,9 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
         {
             const uint32_t nseg = (n + 255u) >> 8;
             uint4* gv = (uint4*)tkey;
-            for (uint32_t g = (uint32_t)wave; g < nseg; g += NW) {
-                const uint32_t q = g * 64u + (uint32_t)lane;   // b128 chunk: times 4q .. 4q + 3
+            const uint32_t tid = opaque(threadIdx.x);   // the scan's addresses are rebuilt per pair, not kept (spilled) across it
+            for (uint32_t g = tid >> 6; g < nseg; g += NW) {
+                const uint32_t q = g * 64u + (tid & 63u);   // b128 chunk: times 4q .. 4q + 3 (tid itself for the first)
                 const bool live = 4u * q < n;
                 const uint4 x = live ? gv[q] : make_uint4(0, 0, 0, 0);
                 const uint32_t local = (x.x >> 16) + (x.y >> 16) + (x.z >> 16) + (x.w >> 16);
@@ -841,16 +882,17 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
         const bool all_lp = used_lp == (LP >= 64 ? ~0ull : ((1ull << LP) - 1ull));
         if (wave == 0 && !all_lp) {
             __builtin_amdgcn_s_setprio(3);
+            const uint32_t lane = opaque(threadIdx.x) & 63u;   // rare path: no address of it kept across pairs
             const uint64_t all = Lc >= 64 ? ~0ull : ((1ull << Lc) - 1ull);
             uint64_t keep = (used_lp << base) & all;
-            const uint64_t mypm = (uint32_t)lane < Lc ? pm[lane] : 0ull;
+            const uint64_t mypm = lane < Lc ? pm[lane] : 0ull;
             for (;;) {
                 const uint64_t par = wave_or_u64(((keep >> lane) & 1ull) ? mypm : 0ull);
                 const uint64_t nk = keep | par;
                 if (nk == keep) break;
                 keep = nk;
             }
-            if ((uint32_t)lane < Lc)
+            if (lane < Lc)
                 remap[lane] = ((keep >> lane) & 1ull)
                                   ? __builtin_amdgcn_mbcnt_hi((uint32_t)(keep >> 32),
                                                               __builtin_amdgcn_mbcnt_lo((uint32_t)keep, 0u))
@@ -963,7 +1005,7 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
         const uint64_t keep = all_lp ? (Lc >= 64 ? ~0ull : ((1ull << Lc) - 1ull)) : *(const uint64_t*)(misc + F3_KEEP);
         const bool ident = all_lp || misc[F3_IDENT] != 0;
         if (!ident && wave == 1) {   // compact the identity-placed layer records in place
-            const uint32_t l = lane;
+            const uint32_t l = opaque(threadIdx.x) & 63u;   // rare path: no address of it kept across pairs
             const uint64_t clo = ((recp)gq->recs + pr)->clo;
             pvac_layer y{};
             if (l < Lc) y = gq->C.layers[clo + l];
@@ -1005,25 +1047,31 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
                 atomicAdd(q + 1, (unsigned long long)l1);
                 atomicAdd(q + 2, (unsigned long long)l2);
             };
-            // first pass from the registers of P1, two products at a time
+            // first pass from the registers of P1, two products at a time: full rounds only, so
+            // every lane has a product
+            const uint32_t full = full_rounds(__builtin_amdgcn_readfirstlane(tid));
 #pragma unroll
             for (int u0 = 0; u0 < U; u0 += 2) {
-                if (__builtin_amdgcn_ballot_w64(prod[u0] != ~0u) == 0) continue;   // none in this wave's rounds
+                if ((uint32_t)u0 >= full) break;   // none in this wave's further rounds
                 ulonglong2 x[2], y[2];
                 uint32_t p[2];
 #pragma unroll
                 for (int v = 0; v < 2; ++v) {
-                    const uint32_t pk = prod[u0 + v] == ~0u ? 0u : prod[u0 + v];
+                    if ((uint32_t)(u0 + v) >= full) break;
+                    const uint32_t pk = prod[u0 + v];
                     x[v] = a_w[pk & 0xFFu];
                     y[v] = b_w[(pk >> 8) & 0xFFu];
                     p[v] = tk16[2u * (pk >> 16)];
                 }
 #pragma unroll
-                for (int v = 0; v < 2; ++v)
-                    if (prod[u0 + v] != ~0u) accumulate(x[v], y[v], p[v]);
+                for (int v = 0; v < 2; ++v) {
+                    if ((uint32_t)(u0 + v) >= full) break;
+                    accumulate(x[v], y[v], p[v]);
+                }
             }
-            // further passes (n > U * BS): recompute
-            for (uint32_t t = tid + U * BS; t < n; t += BS) {
+            M3(11);
+            // further passes (n > U * BS), and every product of a wave with a partial round: recompute
+            for (uint32_t t = tid + (full ? U * BS : 0u); t < n; t += BS) {
                 const uint32_t i = __umulhi(t << 8, mdiv);
                 const uint32_t j = t - i * nB;
                 const ulonglong2 x = a_w[i], y = b_w[j];
@@ -1069,8 +1117,21 @@ __global__ __launch_bounds__(BS, kF3WavesPerSimd) void k_ct_mul_fresh3(const mul
                 // the cell id from limb 2's high dword alone (32-bit shifts): slot at bits 21..31,
                 // channel at bit 20
                 const uint32_t h2 = hi32(l2c);
-                const fp w = fp_fold3_48(l0, l1, l2c & ((1ull << 52) - 1ull));
-                zmask |= __builtin_amdgcn_ballot_w64(!fp_nonzero(w));
+                // The canonical finish (x == p -> 0) and the zero ballot run only in a position round
+                // where some lane can need them (wave-uniform gate). The fold leaves x < 2^127 with
+                // x == sum (mod p), so the sum is 0 mod p only as x = 0 (then x[3] == 0) or x = p
+                // (then x[3] == 0x7FFFFFFF): a lane folds to 0 only inside a gated round, and outside
+                // one x is canonical as it stands. Uniform weights get there about once in 2^30
+                // lanes; a cancelling key, a zero weight and weights below 2^96 always do.
+                uint32_t xw[4];
+                fp_fold3_48_words(l0, l1, l2c & ((1ull << 52) - 1ull), xw);
+                fp w{join32(xw[0], xw[1]), join32(xw[2], xw[3])};
+                if (__builtin_amdgcn_ballot_w64(fp_fold3_48_rare(xw)) != 0) {
+                    M3(9);
+                    w = fp_fold3_48_finish(xw);
+                    zmask |= __builtin_amdgcn_ballot_w64(!fp_nonzero(w));
+                    M3(6);
+                }
                 const uint32_t s = h2 >> 21;
                 const uint32_t lp = __umulhi(s, bdiv);
                 const uint32_t r = s - lp * Bm;

@@ -9,8 +9,17 @@ of the full class (every probed opcode above 3.5 cycles) and listed as unpriced.
 
 The priced cycles of a segment are multiplied by how often a pair runs that code at the bench
 shape (40 x 40 edges, 2 x 2 layers, B = 337):
-  P1, P5 : the text holds U = 4 product rounds; 1,600 products are 25 wave-rounds -> x 25 / 4
+  P1, P5 : the text holds U = 4 product rounds of a wave without a partial round; each of the 8
+           waves runs it once and skips its empty rounds (7 of the 32 at 1,600 products), so 25
+           wave-rounds -> x 25 / 4. With --rounds parent (a source from before the round classes)
+           P1 is priced x 8: there every wave ran the index arithmetic and the LDS reads of all
+           four rounds and skipped only the cell half of an empty one, so x 8 is an upper bound
+           and x 25 / 4 a lower one for that text; P5 skipped an empty pair of rounds as now.
+  loops  : P1's and P5's clamped and masked loops (products past U * 512, and every product of a
+           wave with a partial round): not run at the bench shape -> x 0
   writer : one position round in the text, 21 wave-rounds (about 1,330 emit positions) -> x 21
+  gate   : the writer's canonical finish and zero ballot, run only in a position round where a
+           lane's top word is 0 or 0x7FFFFFFF (about 2^-30 per lane for the bench's weights) -> x 0
   stage  : stage_pair of the next pair, run by the one wave that holds its 40 edges -> x 1
   P2, P4 : the text holds KR = 2 bin rows, a pair has 8 wave-rows of bins -> x 8 / 2
   P3, rest (loop head, barriers, header decode, tail): once per wave -> x 8
@@ -35,11 +44,12 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "pvac_hfhe_cppbyv_amd", "csrc")
 KERNEL = "k_ct_mul_fresh3ILi512E"
-SEGMENTS = collections.OrderedDict([("1", "P1"), ("2", "P2"), ("3", "P3"), ("4", "P4"), ("5", "P5"), ("7", "stage"),
-                                    ("6", "writer")])
+SEGMENTS = collections.OrderedDict([("1", "P1"), ("10", "P1loop"), ("2", "P2"), ("3", "P3"), ("4", "P4"), ("5", "P5"),
+                                    ("11", "P5loop"), ("7", "stage"), ("6", "writer"), ("9", "gate")])
 U, KR = 4, 2
 # runs of a segment's text per pair (see the module text); None: not priced per pair
-TRIPS = {"P1": 25 / U, "P5": 25 / U, "stage": 1.0, "writer": 21.0, "P2": 8 / KR, "P4": 8 / KR, "P3": 8.0, "rest": None}
+TRIPS = {"P1": 25 / U, "P1loop": 0.0, "P5": 25 / U, "P5loop": 0.0, "stage": 1.0, "writer": 21.0, "gate": 0.0, "P2": 8 / KR,
+         "P4": 8 / KR, "P3": 8.0, "rest": None}
 SUFFIX = re.compile(r"_(e32|e64|dpp|sdwa|e64_dpp)$")
 # ISA opcode -> probe row, where the probe's row carries a variant in its name. The probe's plain
 # v_cndmask_b32 row (22.7 cycles) timed a dependent chain through VCC, not the issue cost; the
@@ -94,13 +104,17 @@ def main():
     ap.add_argument("--src", default=os.path.join(CSRC, "k_mul_fresh.hip"), help="another revision of the source")
     ap.add_argument("--probe", default=os.path.join(ROOT, "profiles", "r05", "issue_probe_vcc.json"))
     ap.add_argument("--keep-asm", default=None, help="write the marked ISA here")
+    ap.add_argument("--rounds", choices=("classes", "parent"), default="classes",
+                    help="parent: a source from before the round classes (P1 priced x 8, see the module text)")
     args, flags = ap.parse_known_args()
+    if args.rounds == "parent":
+        TRIPS["P1"] = 8.0
     cost, full_median = probe_costs(args.probe)
     lines = compile_isa(args.src, flags, args.keep_asm)
     start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\S*" + KERNEL + r"\S*:", l))
     end = next(i for i in range(start, len(lines)) if "s_endpgm" in lines[i])
     seg = "rest"
-    count = collections.OrderedDict((s, collections.Counter()) for s in [*SEGMENTS.values(), "rest"])
+    count = collections.OrderedDict((s, collections.Counter()) for s in [*dict.fromkeys(SEGMENTS.values()), "rest"])
     other = collections.Counter()   # non-VALU instructions per segment (reported, not priced)
     for l in lines[start:end]:
         m = re.search(r"PVAC_MARK (\d+)", l)
@@ -138,6 +152,8 @@ def main():
     print()
     print(f"{'segment':<8}{'VALU':>7}{'other':>7}{'cycles/run':>12}{'runs/pair':>11}{'cycles/pair':>13}{'share':>8}")
     for s, n, o, cyc, pp in rows:
+        if n == 0 and o == 0:
+            continue   # a segment this source has no mark for
         if pp is None:
             print(f"{s:<8}{n:>7}{o:>7}{cyc:>12.0f}{'-':>11}{'-':>13}{'-':>8}")
         else:
