@@ -279,7 +279,14 @@ int pvac_hip_check_mul_gsum_path_count(pvac_hip_ctx* ctx, uint64_t out[2]);
  * Nonces: fill_nonces(user, step, first_input, n_words, dev_words, stream) when given (called on
  * the worker thread; fill n_words device words on `stream`, the 2-words-per-output-layer-slot
  * array of pvac_hip_ct_mul_exec), else splitmix64 words: pvac_hip_fill_random with seed
- * nonce_seed + 97 * first_input + step (step counted from 0).
+ * nonce_seed + 97 * first_input + step (step counted from 0). That default is a test stream.
+ * PVAC_CHAIN_DRBG: with fill_nonces and nonces_at null, a step's nonce words come from the worker's
+ * CTR_DRBG (pvac_hip_drbg_fill on the worker's context) instead; with PVAC_MUL_WITH_SIGMA and
+ * salts_at null so do the final step's salts. Hooks, when given, still win; without the flag nothing
+ * changes. Each worker context owns a generator, seeded with 48 bytes drawn from ctx's generator when
+ * the worker is created (and again after ctx's generator is seeded anew by pvac_hip_drbg_seed).
+ * Chunks are handed to workers dynamically, so a run with the flag is not reproducible at
+ * streams > 1 even under an explicit seed; at streams = 1 it is.
  * Outputs are streamed: on_chunk(user, first_input, C, stream) receives each chunk's final
  * c_depth (device batch, capacity-padded CSR) valid until it returns; digest_out (DEVICE, nullable)
  * receives pvac_hip_batch_digest of c_depth for inputs [0, digest_n) (FNV-1a: serial over a cipher's
@@ -318,6 +325,7 @@ int pvac_hip_check_mul_gsum_path_count(pvac_hip_ctx* ctx, uint64_t out[2]);
 #define PVAC_CHAIN_CHECK_GSUM 0x100u
 #define PVAC_CHAIN_STAGE_INPUTS 0x200u   /* ranges j > 0 stage their chunks even on X's device (tests) */
 #define PVAC_CHAIN_IMG_BATCH2 0x400u     /* image -> records conversions in launches of 2 pairs (tests) */
+#define PVAC_CHAIN_DRBG 0x800u           /* default nonces / salts from the workers' CTR_DRBGs, not splitmix */
 #define PVAC_CHAIN_MAX_DEVICES 64
 typedef int (*pvac_chain_step_fn)(void* user, uint32_t step, uint64_t first_input, const pvac_ct_batch* A,
                                   const pvac_ct_batch* X, const pvac_ct_batch* C, uint64_t* dev_words,
@@ -329,7 +337,7 @@ typedef struct pvac_chain_opts {
     uint64_t chunk;        /* inputs per chunk, 0 = 1024 */
     uint64_t nonce_seed;
     uint32_t flags;        /* PVAC_MUL_ORDER_CANONICAL | PVAC_MUL_WITH_SIGMA | PVAC_CHAIN_CHECK_GSUM |
-                              PVAC_CHAIN_STAGE_INPUTS */
+                              PVAC_CHAIN_STAGE_INPUTS | PVAC_CHAIN_DRBG */
     uint32_t pad;
     uint64_t digest_n;     /* leading inputs whose final digests are written */
     uint64_t* digest_out;  /* DEVICE [digest_n], nullable */
@@ -571,8 +579,41 @@ int pvac_hip_gen_fresh_batch_at(pvac_hip_ctx* ctx, uint64_t seed, uint64_t first
  * (core/types.hpp:77-79) for synthetic, shard-invariant batches. out: 2 words per C layer slot. */
 int pvac_hip_fill_nonces(pvac_hip_ctx* ctx, uint64_t seed, uint64_t first_index, const pvac_ct_batch* A,
                          const pvac_ct_batch* B, const pvac_ct_batch* C, uint64_t* out);
-/* splitmix64 stream fill (device): out[i] = splitmix64(seed + (i+1)*golden). */
+/* splitmix64 stream fill (device): out[i] = splitmix64(seed + (i+1)*golden). A reproducible test
+ * stream, predictable from the seed: not for nonces, salts or draws of ciphertext anyone keeps
+ * (pvac_hip_drbg_fill below is). */
 int pvac_hip_fill_random(pvac_hip_ctx* ctx, uint64_t seed, uint64_t* out, size_t n);
+
+/* ---------------------------------------------------------------- device CSPRNG
+ * Every context owns an SP 800-90A rev. 1 CTR_DRBG (AES-256, no derivation function, no prediction
+ * resistance, seedlen 48; csrc/drbg.hpp states the construction). Its state (K, V) lives on the
+ * host; a fill expands K's round keys on the host, hands the keystream AES_K(V + 1 ..) to one kernel
+ * launch on the context's stream and advances the state before it returns, so two fills enqueued
+ * back to back never share a counter. Word 2j of a fill is load_le64 of keystream block j's bytes
+ * 0..7, word 2j + 1 of its bytes 8..15 (the reference's csprng_u64 over the concatenated bytes,
+ * core/random.hpp); an odd request drops the last 8 bytes. One deviation from 90A: no 2^16-byte cap
+ * per request, a fill is one generate call whatever its size.
+ * pvac_hip_drbg_seed instantiates the generator from 48 bytes (NULL: 48 bytes of getrandom(2)). A
+ * context never seeded seeds itself from getrandom at its first fill. A self-seeded generator
+ * reseeds from getrandom after every 2^16 generate calls; an explicitly seeded one never reseeds on
+ * its own, so its stream is reproducible. pvac_hip_drbg_reseed mixes 48 bytes in (NULL: getrandom).
+ * A getrandom failure is PVAC_EDEVICE. pvac_hip_drbg_fill: n_words DEVICE words at out (8-byte
+ * aligned), stream-ordered, not synchronous; n_words = 0 does nothing and is not counted;
+ * PVAC_EINVAL for a null out with n_words > 0. Timing label "aes256_ctr".
+ * pvac_hip_drbg_counts: out[0] generate calls, out[1] keystream blocks, out[2] reseeds since the
+ * generator was seeded, out[3] = 1 when it seeded itself.
+ * pvac_hip_aes256_ctr is the kernel alone (tests and diagnostics, like pvac_hip_fill_random): the
+ * keystream AES_key(ctr + j), j = 0.., ctr a 128-bit big-endian integer (all 16 bytes count, mod 2^128).
+ * The round keys travel in the kernel's arguments; the library writes no key to a device buffer.
+ * pvac_hip_drbg_tile (host only): out[0] = keystream blocks one workgroup pass covers, out[1] = the
+ * most workgroups a launch uses (a persistent grid strides over the tiles beyond that). */
+int pvac_hip_aes256_ctr(pvac_hip_ctx* ctx, const uint8_t key[32], const uint8_t ctr_be[16], uint64_t* out_dev,
+                        size_t n_words);
+int pvac_hip_drbg_seed(pvac_hip_ctx* ctx, const uint8_t seed[48]);
+int pvac_hip_drbg_reseed(pvac_hip_ctx* ctx, const uint8_t entropy[48]);
+int pvac_hip_drbg_fill(pvac_hip_ctx* ctx, uint64_t* out_dev, size_t n_words);
+int pvac_hip_drbg_counts(pvac_hip_ctx* ctx, uint64_t out[4]);
+int pvac_hip_drbg_tile(uint32_t out[2]);
 /* Host-only: the bucket count std::unordered_map::reserve(n) picks on this libstdc++ (the
  * emit-order pin of ct_mul, ops/arithmetic.hpp:75-76). No device access. */
 uint64_t pvac_hip_bucket_count(uint64_t n);

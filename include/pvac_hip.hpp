@@ -70,6 +70,13 @@ struct Error : std::runtime_error {
 
 using RandomSource = std::function<uint64_t()>;
 
+// In place of a RandomSource in the batched forms (ct_mul_batch, enc_value_batch, ct_mul_chain): nonces,
+// salts and draws are filled on the device by the context's CTR_DRBG (pvac_hip_drbg_fill: AES-256,
+// seeded from getrandom), no word is drawn, staged or uploaded by the host. The stream is not the
+// reference's draw order, so these forms cannot replay a recorded stream; the RandomSource forms can.
+struct DeviceRandom {};
+inline constexpr DeviceRandom device_random{};
+
 // One 8-byte getrandom per word, as csprng_u64 does (core/random.hpp:106-110).
 inline uint64_t os_random_u64() {
     uint64_t v = 0;
@@ -553,6 +560,20 @@ public:
     template <class PubKeyT, class CipherT>
     std::vector<CipherT> ct_mul(const PubKeyT& pk, const std::vector<const CipherT*>& A,
                                 const std::vector<const CipherT*>& B, bool with_sigma, const RandomSource& rnd) {
+        return ct_mul_from(pk, A, B, with_sigma, &rnd);
+    }
+    // ... with every nonce and salt from the device generator: nothing is drawn or uploaded by the host
+    template <class PubKeyT, class CipherT>
+    std::vector<CipherT> ct_mul(const PubKeyT& pk, const std::vector<const CipherT*>& A,
+                                const std::vector<const CipherT*>& B, bool with_sigma, DeviceRandom) {
+        return ct_mul_from(pk, A, B, with_sigma, nullptr);
+    }
+
+private:
+    // rnd == nullptr: device_random
+    template <class PubKeyT, class CipherT>
+    std::vector<CipherT> ct_mul_from(const PubKeyT& pk, const std::vector<const CipherT*>& A,
+                                     const std::vector<const CipherT*>& B, bool with_sigma, const RandomSource* rnd) {
         if (A.size() != B.size()) throw Error(PVAC_EINVAL, "ct_mul: |A| != |B|");
         const size_t n = A.size();
         if (!n) return {};
@@ -580,22 +601,28 @@ public:
         pvac_ct_batch vc = c.plan_view();
         pvac_hip_plan plan{};
         check(pvac_hip_ct_mul_plan(ctx_, &va, &vb, &vc, &plan));
-        // nonces per pair in the reference's draw order: (la, lb) row-major, lo then hi
-        std::vector<uint64_t> loff(n);
-        c.d_l_off.download(loff.data(), n, stream_);
-        detail::hip_ok(hipStreamSynchronize(stream_), "sync");
-        std::vector<uint64_t> nonces(2 * (plan.total_layer_slots ? plan.total_layer_slots : 1), 0);
-        for (size_t i = 0; i < n; ++i) {
-            const uint64_t LA = A[i]->L.size(), LB = B[i]->L.size();
-            const uint64_t s0 = loff[i] + LA + LB;
-            for (uint64_t k = 0; k < LA * LB; ++k) {
-                nonces[2 * (s0 + k)] = rnd();
-                nonces[2 * (s0 + k) + 1] = rnd();
-            }
-        }
         detail::dev_array<uint64_t>& d_nonces = mul_nonces_;
-        d_nonces.alloc(nonces.size());
-        d_nonces.upload(nonces.data(), nonces.size(), stream_);
+        const size_t nonce_words = 2 * (plan.total_layer_slots ? plan.total_layer_slots : 1);
+        d_nonces.alloc(nonce_words);
+        if (rnd) {
+            // nonces per pair in the reference's draw order: (la, lb) row-major, lo then hi
+            std::vector<uint64_t> loff(n);
+            c.d_l_off.download(loff.data(), n, stream_);
+            detail::hip_ok(hipStreamSynchronize(stream_), "sync");
+            std::vector<uint64_t> nonces(nonce_words, 0);
+            for (size_t i = 0; i < n; ++i) {
+                const uint64_t LA = A[i]->L.size(), LB = B[i]->L.size();
+                const uint64_t s0 = loff[i] + LA + LB;
+                for (uint64_t k = 0; k < LA * LB; ++k) {
+                    nonces[2 * (s0 + k)] = (*rnd)();
+                    nonces[2 * (s0 + k) + 1] = (*rnd)();
+                }
+            }
+            d_nonces.upload(nonces.data(), nonces.size(), stream_);
+        } else {
+            // one fill over every layer slot's two words: only the product layers' are read
+            check(pvac_hip_drbg_fill(ctx_, d_nonces.p, nonce_words));
+        }
         c.alloc_rows(n, plan.total_layer_slots, plan.total_edge_slots, sigma_words(), with_sigma);
         lap(phases_.plan);
         vc = c.out_view(n, false);
@@ -611,19 +638,25 @@ public:
             detail::dev_array<uint32_t>& d_status = mul_status_;
             d_status.alloc(n);
             check(pvac_hip_ct_mul_status(ctx_, d_status.p, n));
-            c.d_e_cnt.download(ecnt.data(), n, stream_);
-            c.d_e_off.download(eoff.data(), n, stream_);
+            if (rnd) {
+                c.d_e_cnt.download(ecnt.data(), n, stream_);
+                c.d_e_off.download(eoff.data(), n, stream_);
+            }
             d_status.download(status.data(), n, stream_);
             detail::hip_ok(hipStreamSynchronize(stream_), "sync");
-            std::vector<uint64_t> salts(plan.total_edge_slots ? plan.total_edge_slots : 1, 0);
-            bool hash_order = true;
-            for (size_t i = 0; i < n; ++i) {
-                hash_order &= status[i] != 1u;
-                for (uint64_t k = 0; k < ecnt[i]; ++k) salts[eoff[i] + k] = rnd();
-            }
+            const size_t salt_words = plan.total_edge_slots ? plan.total_edge_slots : 1;
             detail::dev_array<uint64_t>& d_salts = mul_salts_;
-            d_salts.alloc(salts.size());
-            d_salts.upload(salts.data(), salts.size(), stream_);
+            d_salts.alloc(salt_words);
+            bool hash_order = true;
+            for (size_t i = 0; i < n; ++i) hash_order &= status[i] != 1u;
+            if (rnd) {
+                std::vector<uint64_t> salts(salt_words, 0);
+                for (size_t i = 0; i < n; ++i)
+                    for (uint64_t k = 0; k < ecnt[i]; ++k) salts[eoff[i] + k] = (*rnd)();
+                d_salts.upload(salts.data(), salts.size(), stream_);
+            } else {
+                check(pvac_hip_drbg_fill(ctx_, d_salts.p, salt_words));   // a salt per edge slot
+            }
             vc = c.out_view(n, true);
             if (hash_order) {
                 check(pvac_hip_sigma_batch(ctx_, &vc, d_salts.p));
@@ -650,6 +683,8 @@ public:
         return out;
     }
 
+public:
+
     // Depth chains through pvac_hip_ct_mul_chain (the chain entry point): for every input x of xs,
     // c_0 = x, c_k = ct_mul(pk, c_{k-1}, x) for k = 1..depth (the test_depth / cfg-4 shape of
     // tests/test_main.cpp:289-293's loop); returns every c_depth. Randomness of chain i comes from
@@ -669,8 +704,25 @@ public:
                                       bool with_sigma, std::vector<RandomSource>& rnds,
                                       const std::vector<int>& devices = {}, uint32_t streams = 2, uint64_t chunk = 16,
                                       const std::vector<std::vector<const CipherT*>>& ops = {}) {
+        if (rnds.size() != xs.size()) throw Error(PVAC_EINVAL, "ct_mul_chain: one RandomSource per input");
+        return chain_from(pk, xs, depth, with_sigma, &rnds, devices, streams, chunk, ops);
+    }
+    // ... with the workers' device generators (PVAC_CHAIN_DRBG): no hook draws, stages or uploads a word
+    template <class PubKeyT, class CipherT>
+    std::vector<CipherT> ct_mul_chain(const PubKeyT& pk, const std::vector<const CipherT*>& xs, uint32_t depth,
+                                      bool with_sigma, DeviceRandom, const std::vector<int>& devices = {},
+                                      uint32_t streams = 2, uint64_t chunk = 16,
+                                      const std::vector<std::vector<const CipherT*>>& ops = {}) {
+        return chain_from<PubKeyT, CipherT>(pk, xs, depth, with_sigma, nullptr, devices, streams, chunk, ops);
+    }
+
+private:
+    // rnds == nullptr: device_random
+    template <class PubKeyT, class CipherT>
+    std::vector<CipherT> chain_from(const PubKeyT& pk, const std::vector<const CipherT*>& xs, uint32_t depth,
+                                    bool with_sigma, std::vector<RandomSource>* rnds, const std::vector<int>& devices,
+                                    uint32_t streams, uint64_t chunk, const std::vector<std::vector<const CipherT*>>& ops) {
         const size_t n = xs.size();
-        if (rnds.size() != n) throw Error(PVAC_EINVAL, "ct_mul_chain: one RandomSource per input");
         if (ops.size() > depth) throw Error(PVAC_EINVAL, "ct_mul_chain: more operand steps than depth");
         for (const auto& y : ops)
             if (y.size() != n) throw Error(PVAC_EINVAL, "ct_mul_chain: one operand per input and step");
@@ -687,12 +739,12 @@ public:
             std::vector<CipherT> out;
             uint32_t depth, m_bits;
             bool sigma;
-        } stt{&rnds, std::vector<CipherT>(n), depth, prm_.m_bits, with_sigma};
+        } stt{rnds, std::vector<CipherT>(n), depth, prm_.m_bits, with_sigma};
         pvac_chain_opts o{};
         o.depth = depth;
         o.streams = streams;
         o.chunk = chunk;
-        o.flags = with_sigma ? PVAC_MUL_WITH_SIGMA : 0u;
+        o.flags = (with_sigma ? PVAC_MUL_WITH_SIGMA : 0u) | (rnds ? 0u : PVAC_CHAIN_DRBG);
         o.user = &stt;
         o.devices = devices.empty() ? nullptr : devices.data();
         o.n_devices = (uint32_t)devices.size();
@@ -761,10 +813,13 @@ public:
                 return 1;
             }
         };
+        if (!rnds) o.nonces_at = o.after_step = o.salts_at = nullptr;   // the workers' generators fill
         pvac_chain_stats st{};
         check(pvac_hip_ct_mul_chain(ctx_, &vx, &o, &st));
         return std::move(stt.out);
     }
+
+public:
 
     // Batched ct_add / ct_sub (ops/arithmetic.hpp:12-31, 43-45); sigmas carried through.
     template <class CipherT>
@@ -865,7 +920,7 @@ public:
         std::vector<uint64_t> draws((size_t)n * stride);
         for (auto& x : draws) x = rnd();
         std::vector<uint32_t> status;
-        std::vector<CipherT> out = enc_run<CipherT>(vs, draws, stride, lpv, epv, with_sigma, status, depth_hint);
+        std::vector<CipherT> out = enc_run<CipherT>(vs, &draws, stride, lpv, epv, with_sigma, status, depth_hint);
         for (uint32_t grow = stride; ; grow *= 2) {
             std::vector<size_t> redo;
             for (size_t i = 0; i < n; ++i) {
@@ -882,7 +937,7 @@ public:
                 for (uint32_t j = stride; j < s2; ++j) d2[k * s2 + j] = rnd();
             }
             std::vector<uint32_t> st2;
-            std::vector<CipherT> o2 = enc_run<CipherT>(v2, d2, s2, lpv, epv, with_sigma, st2, depth_hint);
+            std::vector<CipherT> o2 = enc_run<CipherT>(v2, &d2, s2, lpv, epv, with_sigma, st2, depth_hint);
             // the redone values' draws become their prefix for a further round
             std::vector<uint64_t> nd((size_t)n * s2, 0);
             for (size_t i = 0; i < n; ++i) std::memcpy(&nd[i * s2], &draws[i * stride], (size_t)stride * 8);
@@ -893,6 +948,43 @@ public:
             }
             draws.swap(nd);
             stride = s2;
+        }
+        return out;
+    }
+
+    // ... with the draws filled on the device: value i takes `stride` words of one pvac_hip_drbg_fill.
+    // A value whose rejection sampling outruns its stride (status 1) is encrypted again from fresh
+    // draws of twice the stride (there is no stream to keep a prefix of).
+    template <class PubKeyT, class SecKeyT, class CipherT>
+    std::vector<CipherT> enc_value(const PubKeyT& pk, const SecKeyT& sk, const std::vector<uint64_t>& vs,
+                                   bool with_sigma, DeviceRandom, int depth_hint = 0) {
+        const size_t n = vs.size();
+        if (!n) return {};
+        ensure_keys(pk, sk);
+        if (with_sigma) ensure_H(pk);
+        uint32_t lpv = 0, epv = 0, stride = 0;
+        check(pvac_hip_enc_caps_depth(ctx_, depth_hint, &lpv, &epv, &stride));
+        std::vector<uint32_t> status;
+        std::vector<CipherT> out = enc_run<CipherT>(vs, nullptr, stride, lpv, epv, with_sigma, status, depth_hint);
+        for (;;) {
+            std::vector<size_t> redo;
+            std::vector<uint64_t> v2;
+            for (size_t i = 0; i < n; ++i) {
+                if (status[i] == 2) throw Error(PVAC_EINVAL, "enc_value: a merged edge group cancelled (p ~ 1/p)");
+                if (status[i] == 1) {
+                    redo.push_back(i);
+                    v2.push_back(vs[i]);
+                }
+            }
+            if (redo.empty()) break;
+            if (stride > (1u << 20)) throw Error(PVAC_EINVAL, "enc_value: the draws keep being rejected");
+            stride *= 2;
+            std::vector<uint32_t> st2;
+            std::vector<CipherT> o2 = enc_run<CipherT>(v2, nullptr, stride, lpv, epv, with_sigma, st2, depth_hint);
+            for (size_t k = 0; k < redo.size(); ++k) {
+                out[redo[k]] = std::move(o2[k]);
+                status[redo[k]] = st2[k];
+            }
         }
         return out;
     }
@@ -1462,13 +1554,15 @@ private:
 
     // one pvac_hip_enc_value launch over (vs, draws) with a fixed stride; status per value
     template <class CipherT>
-    std::vector<CipherT> enc_run(const std::vector<uint64_t>& vs, const std::vector<uint64_t>& draws, uint32_t stride,
+    // draws == nullptr: n * stride words of the device generator
+    std::vector<CipherT> enc_run(const std::vector<uint64_t>& vs, const std::vector<uint64_t>* draws, uint32_t stride,
                                  uint32_t lpv, uint32_t epv, bool with_sigma, std::vector<uint32_t>& status,
                                  int depth_hint = 0) {
         const size_t n = vs.size();
-        detail::dev_array<uint64_t> d_v(n), d_r(draws.size());
+        detail::dev_array<uint64_t> d_v(n), d_r(draws ? draws->size() : n * (size_t)stride);
         d_v.upload(vs.data(), n, stream_);
-        d_r.upload(draws.data(), draws.size(), stream_);
+        if (draws) d_r.upload(draws->data(), draws->size(), stream_);
+        else check(pvac_hip_drbg_fill(ctx_, d_r.p, n * (size_t)stride));
         detail::batch c;
         c.alloc_index(n);
         const uint64_t lslots = (uint64_t)n * lpv, eslots = (uint64_t)n * epv;
@@ -1578,6 +1672,16 @@ std::vector<CipherT> ct_mul_batch(const PubKeyT& pk, const std::vector<CipherT>&
     return engine_for(pk).ct_mul(pk, a, b, with_sigma, rnd);
 }
 
+// Nonces and salts from the device generator (device_random): no per-word host work, no upload.
+template <class PubKeyT, class CipherT>
+std::vector<CipherT> ct_mul_batch(const PubKeyT& pk, const std::vector<CipherT>& A, const std::vector<CipherT>& B,
+                                  bool with_sigma, DeviceRandom) {
+    std::vector<const CipherT*> a, b;
+    for (auto& x : A) a.push_back(&x);
+    for (auto& x : B) b.push_back(&x);
+    return engine_for(pk).ct_mul(pk, a, b, with_sigma, device_random);
+}
+
 // Multi-device batch: pairs split into contiguous ranges, one per entry of `devices` (an ordinal may
 // repeat), each range on its own host thread and context. Draws from rnd stay in the one-device order:
 // every pair's nonces first (pair order; their counts, 2 |A.L| |B.L| per pair, are known up front, so
@@ -1661,6 +1765,15 @@ std::vector<CipherT> ct_mul_chain(const PubKeyT& pk, const std::vector<CipherT>&
     std::vector<const CipherT*> x;
     for (auto& c : xs) x.push_back(&c);
     return engine_for(pk).ct_mul_chain(pk, x, depth, with_sigma, rnds, devices);
+}
+
+// ... with the chain workers' device generators: not reproducible (chunks go to workers as they come).
+template <class PubKeyT, class CipherT>
+std::vector<CipherT> ct_mul_chain(const PubKeyT& pk, const std::vector<CipherT>& xs, uint32_t depth, bool with_sigma,
+                                  DeviceRandom, const std::vector<int>& devices = {}) {
+    std::vector<const CipherT*> x;
+    for (auto& c : xs) x.push_back(&c);
+    return engine_for(pk).ct_mul_chain(pk, x, depth, with_sigma, device_random, devices);
 }
 
 // The reference's loop c_k = ct_mul(c_{k-1}, y_k) with a fresh operand per step (tests/test_main.cpp:
@@ -1865,6 +1978,12 @@ template <class CipherT, class PubKeyT, class SecKeyT>
 std::vector<CipherT> enc_value_batch(const PubKeyT& pk, const SecKeyT& sk, const std::vector<uint64_t>& vs,
                                      bool with_sigma = true, const RandomSource& rnd = os_random_u64) {
     return engine_for(pk).template enc_value<PubKeyT, SecKeyT, CipherT>(pk, sk, vs, with_sigma, rnd);
+}
+
+template <class CipherT, class PubKeyT, class SecKeyT>
+std::vector<CipherT> enc_value_batch(const PubKeyT& pk, const SecKeyT& sk, const std::vector<uint64_t>& vs,
+                                     bool with_sigma, DeviceRandom) {
+    return engine_for(pk).template enc_value<PubKeyT, SecKeyT, CipherT>(pk, sk, vs, with_sigma, device_random);
 }
 
 template <class PubKeyT, class SecKeyT, class CipherT>

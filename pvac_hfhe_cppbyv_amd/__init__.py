@@ -30,6 +30,7 @@ MUL_WITH_SIGMA, MUL_ORDER_CANONICAL = 0x1, 0x2
 CHAIN_CHECK_GSUM = 0x100
 CHAIN_STAGE_INPUTS = 0x200
 CHAIN_IMG_BATCH2 = 0x400
+CHAIN_DRBG = 0x800
 CHAIN_MAX_DEPTH = 32
 LAYER_LIMIT_DEFAULT, LAYER_LIMIT_MAX = 16384, 1 << 24
 ENC_WITH_SIGMA = 0x1
@@ -197,6 +198,12 @@ def load_library(path: str = _LIB_PATH) -> C.CDLL:
         "pvac_hip_gen_fresh_batch_at": ([vp, u64, u64, u32, C.POINTER(CtBatch)], i32),
         "pvac_hip_fill_nonces": ([vp, u64, u64, C.POINTER(CtBatch), C.POINTER(CtBatch), C.POINTER(CtBatch), vp], i32),
         "pvac_hip_fill_random": ([vp, u64, vp, C.c_size_t], i32),
+        "pvac_hip_aes256_ctr": ([vp, vp, vp, vp, C.c_size_t], i32),
+        "pvac_hip_drbg_seed": ([vp, vp], i32),
+        "pvac_hip_drbg_reseed": ([vp, vp], i32),
+        "pvac_hip_drbg_fill": ([vp, vp, C.c_size_t], i32),
+        "pvac_hip_drbg_counts": ([vp, C.POINTER(u64)], i32),
+        "pvac_hip_drbg_tile": ([C.POINTER(u32)], i32),
         "pvac_hip_batch_digest": ([vp, C.POINTER(CtBatch), vp], i32),
         "pvac_hip_batch_sumdigest": ([vp, C.POINTER(CtBatch), vp], i32),
         "pvac_hip_commit_ct": ([vp, C.POINTER(CtBatch), vp], i32),
@@ -443,13 +450,18 @@ class Engine:
         self._check(self.lib.pvac_hip_enc_caps_depth(self.ctx, int(depth), C.byref(lp), C.byref(ep), C.byref(dh)))
         return lp.value, ep.value, dh.value
 
-    def enc_value(self, values, rnd, sigma=False, depth=0):
+    def enc_value(self, values, rnd=None, sigma=False, depth=0):
         """values: n u64 (host array or device tensor); rnd: (n, stride) u64 draws per value (the
-        reference's csprng_u64 stream). depth > 0: enc_value_depth (ops/encrypt.hpp:281-287); a value
-        of 0 is enc_zero_depth (:293-298). Returns (DeviceBatch, status numpy u32)."""
+        reference's csprng_u64 stream), or None: n * draws_hint (enc_caps) words of the engine's
+        CTR_DRBG, filled on the device (drbg_fill). depth > 0: enc_value_depth
+        (ops/encrypt.hpp:281-287); a value of 0 is enc_zero_depth (:293-298). Returns (DeviceBatch,
+        status numpy u32)."""
         torch = self.torch
         if isinstance(values, np.ndarray) or isinstance(values, list):
             values = _t(np.ascontiguousarray(np.asarray(values, dtype=np.uint64))).to(self.device)
+        if rnd is None:
+            rnd = torch.empty(max(values.numel() * self.enc_caps(depth)[2], 1), dtype=torch.int64, device=self.device)
+            self.drbg_fill(rnd)
         if isinstance(rnd, np.ndarray):
             rnd = _t(np.ascontiguousarray(rnd, np.uint64)).to(self.device)
         n = values.numel()
@@ -595,9 +607,13 @@ class Engine:
         return C_, plan
 
     def ct_mul(self, A: DeviceBatch, B: DeviceBatch, nonces=None, salts=None, flags=0, C_=None, plan=None,
-               nonce_seed=None):
+               nonce_seed=None, secure=False):
         """Batched ct_mul. nonces: device int64 tensor parallel to output layer slots (2 words each);
-        if None, filled from a splitmix stream (nonce_seed) on the device."""
+        if None, filled from a splitmix stream (nonce_seed) on the device: a reproducible test stream,
+        predictable from the seed. secure=True: with nonces None the array is one drbg_fill over all
+        2 * total_layer_slots words (only the product-layer slots are read; the other words are
+        discarded), and with MUL_WITH_SIGMA and salts None it is followed by one fill of
+        total_edge_slots salts."""
         torch = self.torch
         if C_ is None or plan is None:
             C_, plan = self.ct_mul_plan(A, B)
@@ -611,7 +627,13 @@ class Engine:
                 C_.sigma = torch.empty((e, 128), dtype=torch.int64, device=self.device)
         if nonces is None:
             nonces = torch.empty(2 * max(plan.total_layer_slots, 1), dtype=torch.int64, device=self.device)
-            self.fill_random(nonces, 0x5EED0003 if nonce_seed is None else nonce_seed)
+            if secure:
+                self.drbg_fill(nonces)
+            else:
+                self.fill_random(nonces, 0x5EED0003 if nonce_seed is None else nonce_seed)
+        if secure and salts is None and flags & MUL_WITH_SIGMA:
+            salts = torch.empty(max(plan.total_edge_slots, 1), dtype=torch.int64, device=self.device)
+            self.drbg_fill(salts)
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         sa, sb, sc = A.struct(), B.struct(), C_.struct()
         self._check(self.lib.pvac_hip_ct_mul_exec(self.ctx, C.byref(plan), C.byref(sa), C.byref(sb), p(nonces),
@@ -654,7 +676,7 @@ class Engine:
     def ct_mul_chain(self, X: DeviceBatch, depth, nonce_seed=0x5EED0040, streams=4, chunk=1024, check_gsum=False,
                      digest_n=0, canonical=False, fill_nonces=None, on_chunk=None, count_n=None, sigma=False,
                      devices=None, stage_inputs=False, nonces_at=None, after_step=None, salts_at=None,
-                     sumdigest=False, operands=None, img_batch2=False):
+                     sumdigest=False, operands=None, img_batch2=False, secure=False):
         """c_0 = x, c_k = ct_mul(c_{k-1}, x) to `depth` for every input x of X (tests/test_main.cpp:289-295)
         on `streams` internal worker streams in chunks of `chunk` inputs (pvac_hip_ct_mul_chain).
         Returns a dict of the call's statistics; with digest_n > 0 also the final digests / edge
@@ -668,7 +690,9 @@ class Engine:
         whose pvac_hip_batch_sumdigest is returned. operands: DeviceBatches of |X| ciphers, step d
         multiplying by operands[d] (the reference's loop with a fresh enc_value per step,
         tests/test_main.cpp:291-292), later steps by X. img_batch2: image conversions in launches of
-        two pairs (tests)."""
+        two pairs (tests). secure: nonces (and the final step's salts) no hook fills come from the
+        workers' CTR_DRBGs (PVAC_CHAIN_DRBG) instead of splitmix by nonce_seed; reproducible under
+        drbg_seed only at streams=1."""
         torch = self.torch
         dn = min(int(digest_n), X.n)
         cn = dn if count_n is None else min(int(count_n), X.n)
@@ -685,7 +709,7 @@ class Engine:
         o = ChainOpts(depth=depth, streams=streams, chunk=chunk, nonce_seed=nonce_seed,
                       flags=(CHAIN_CHECK_GSUM if check_gsum else 0) | (MUL_ORDER_CANONICAL if canonical else 0) |
                       (MUL_WITH_SIGMA if sigma else 0) | (CHAIN_STAGE_INPUTS if stage_inputs else 0) |
-                      (CHAIN_IMG_BATCH2 if img_batch2 else 0),
+                      (CHAIN_IMG_BATCH2 if img_batch2 else 0) | (CHAIN_DRBG if secure else 0),
                       pad=0, digest_n=dn, digest_out=C.c_void_p(dig.data_ptr()) if dn else None,
                       count_n=cn, count_out=C.c_void_p(cnt.data_ptr()) if cn else None,
                       fill_nonces=fill_nonces or FILL_NONCES_CB(), on_chunk=on_chunk or ON_CHUNK_CB(), user=None,
@@ -1059,8 +1083,56 @@ class Engine:
 
     # ---- synthetic inputs / checks
     def fill_random(self, t, seed):
+        """splitmix64 words: a reproducible test stream, not for ciphertext anyone keeps (drbg_fill is)."""
         self._check(self.lib.pvac_hip_fill_random(self.ctx, seed, C.c_void_p(t.data_ptr()), t.numel()))
         return t
+
+    # ---- the device CSPRNG (include/pvac_hip.h: AES-256 CTR_DRBG, state on the host, keystream by a kernel)
+    @staticmethod
+    def _seed48(b, what):
+        if b is None:
+            return None
+        b = bytes(b)
+        if len(b) != 48:
+            raise PvacError(f"{what}: 48 bytes, not {len(b)}")
+        return C.create_string_buffer(b, 48)
+
+    def drbg_seed(self, seed=None):
+        """Instantiate the generator from 48 bytes (None: getrandom). An explicit seed makes every
+        later fill reproducible and switches the automatic reseeds off."""
+        self._check(self.lib.pvac_hip_drbg_seed(self.ctx, self._seed48(seed, "drbg_seed")))
+
+    def drbg_reseed(self, entropy=None):
+        self._check(self.lib.pvac_hip_drbg_reseed(self.ctx, self._seed48(entropy, "drbg_reseed")))
+
+    def drbg_fill(self, t):
+        """Fill the int64 device tensor t (contiguous) with generator words, stream-ordered; returns t."""
+        self._check(self.lib.pvac_hip_drbg_fill(self.ctx, C.c_void_p(t.data_ptr()) if t.numel() else None, t.numel()))
+        return t
+
+    def aes256_ctr(self, key, ctr, n, out=None):
+        """The raw keystream AES_key(ctr + j) as n u64 words (device int64 tensor): key 32 bytes, ctr
+        16 bytes big-endian. out: a tensor of at least n words to write instead of a new one."""
+        key, ctr = bytes(key), bytes(ctr)
+        if len(key) != 32 or len(ctr) != 16:
+            raise PvacError("aes256_ctr: a 32-byte key and a 16-byte counter block")
+        if out is None:
+            out = self.torch.empty(max(n, 1), dtype=self.torch.int64, device=self.device)
+        self._check(self.lib.pvac_hip_aes256_ctr(self.ctx, C.create_string_buffer(key, 32), C.create_string_buffer(ctr, 16),
+                                                 C.c_void_p(out.data_ptr()), n))
+        return out[:n]
+
+    def drbg_counts(self):
+        """(generate calls, keystream blocks, reseeds, self-seeded 0/1) since the generator was seeded."""
+        v = (C.c_uint64 * 4)()
+        self._check(self.lib.pvac_hip_drbg_counts(self.ctx, v))
+        return tuple(int(x) for x in v)
+
+    def drbg_tile(self):
+        """(keystream blocks per workgroup pass, most workgroups of a launch)."""
+        v = (C.c_uint32 * 2)()
+        self._check(self.lib.pvac_hip_drbg_tile(v), None)
+        return int(v[0]), int(v[1])
 
     def gen_fresh(self, n, seed, edges_per_layer=20, first_index=0):
         """cfg-3 synthetic fresh-shaped ciphers; cipher i is keyed by global index first_index + i."""
@@ -1301,5 +1373,5 @@ class Engine:
 
 
 __all__ = ["Engine", "DeviceBatch", "HostCipher", "PvacError", "LAYER_DT", "load_library", "FP_ADD", "FP_SUB",
-           "FP_MUL", "FP_NEG", "FP_SCALE", "FP_INV", "MUL_WITH_SIGMA", "MUL_ORDER_CANONICAL", "CHAIN_CHECK_GSUM", "CHAIN_STAGE_INPUTS", "STEP_CB",
+           "FP_MUL", "FP_NEG", "FP_SCALE", "FP_INV", "MUL_WITH_SIGMA", "MUL_ORDER_CANONICAL", "CHAIN_CHECK_GSUM", "CHAIN_STAGE_INPUTS", "CHAIN_DRBG", "STEP_CB",
            "ChainOpts", "ChainStats", "FILL_NONCES_CB", "ON_CHUNK_CB"]

@@ -100,5 +100,13 @@ __host__ __device__ inline void aes256_encrypt(uint32_t& w0, uint32_t& w1, uint3
     w0 = n0 ^ rk(56); w1 = n1 ^ rk(57); w2 = n2 ^ rk(58); w3 = n3 ^ rk(59);
 }
 
+// A counter-mode keystream request over the full 128-bit block (csrc/drbg.hpp, k_drbg.hip): block j
+// (0 <= j < nb) is AES_K(ctr + j mod 2^128) with the counter block read big-endian, ctr = hi * 2^64 + lo.
+// Keystream word 2j is load_le64 of block j's bytes 0..7, word 2j + 1 of its bytes 8..15.
+struct aes_ctr_job {
+    uint32_t rk[60];        // the expanded key (aes256_expand)
+    uint64_t ctr_hi, ctr_lo;
+    uint64_t nb;
+};
 
 }  // namespace pvhip

@@ -76,6 +76,11 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* p
 hipError_t launch_fp_binop(int op, const uint64_t* alo, const uint64_t* ahi, const uint64_t* blo,
                            const uint64_t* bhi, uint64_t* clo, uint64_t* chi, size_t n, hipStream_t st);
 hipError_t launch_fill_random(uint64_t seed, uint64_t* out, size_t n, hipStream_t st);
+// the AES-256 counter-mode keystream of a job (aes256.hpp, k_drbg.hip): out[0, n_words), n_words <= 2 nb.
+// A workgroup pass covers kDrbgTile blocks; the persistent grid has at most kDrbgGridCap workgroups.
+struct aes_ctr_job;
+constexpr uint32_t kDrbgTile = 1024, kDrbgGridCap = 512;
+hipError_t launch_aes256_ctr(const aes_ctr_job& job, uint64_t* out, size_t n_words, hipStream_t st);
 hipError_t launch_gen_fresh(uint64_t seed, uint64_t first, uint32_t epl, uint32_t B, const pvac_ct_batch& X,
                             hipStream_t st);
 hipError_t launch_fill_nonces(uint64_t seed, uint64_t first, const pvac_ct_batch& A, const pvac_ct_batch& B,

@@ -17,6 +17,7 @@
 
 #include "common.hpp"
 #include "dev_mem.hpp"
+#include "drbg.hpp"
 #include "large_plan.hpp"
 #include "sigma.hpp"
 
@@ -258,6 +259,11 @@ struct pvac_hip_ctx {
         const uint64_t* dst_index[4] = {};          // and dst's l_off, l_cnt, e_off, e_cnt
         uint64_t path[4] = {};                      // execs wide / 8-byte sigma path, tiles dealt, output ciphers
     } gather;
+    struct {   // the CTR_DRBG behind pvac_hip_drbg_* (rt_drbg.cpp, drbg.hpp, k_drbg.hip)
+        pvhip::ctr_drbg gen;            // its own mutex guards the state
+        uint64_t epoch = 0;             // bumped by pvac_hip_drbg_seed (a chain worker's generator follows it)
+        uint64_t worker_from = ~0ull;   // a chain worker: the parent's epoch its seed was drawn at (~0: not yet)
+    } drbg;
     struct {
         bool on = false;
         std::map<std::string, pvhip::timer_rec> timers;
@@ -454,6 +460,9 @@ struct step_images {
 // rt_mul.cpp: pvac_hip_ct_mul_exec, with a chain step's images (all null for a caller's batch)
 int ct_mul_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_ct_batch* A, const pvac_ct_batch* B,
                 const uint64_t* nonces, const uint64_t* salts, pvac_ct_batch* C, uint32_t flags, step_images img);
+
+// rt_drbg.cpp: n words of the context's generator into out on the context's stream (pvac_hip_drbg_fill)
+int drbg_fill(pvac_hip_ctx* c, uint64_t* out, size_t n_words, const char* where);
 
 // rt_add.cpp: pvac_hip_ct_add_exec with the most layers a pair may have. The ABI entry passes
 // max(kAddLdsLayers, the context's layer limit); ct_recrypt's and ct_lincomb's sums pass kAddLdsLayers,

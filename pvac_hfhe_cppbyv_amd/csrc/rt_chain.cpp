@@ -110,6 +110,11 @@ bool chain_final_sigma(pvac_hip_ctx* k, chain_shared* sh, uint32_t d, uint64_t c
             sh->failed(PVAC_EINVAL, "ct_mul_chain: salts_at callback failed");
             return false;
         }
+    } else if (o.flags & PVAC_CHAIN_DRBG) {
+        if (drbg_fill(k, k->worker.salts.get(), (size_t)slots, "sigma fill salts")) {
+            sh->failed(PVAC_EDEVICE, "ct_mul_chain: " + k->err);
+            return false;
+        }
     } else if (!chain_ok(sh,
                          launch_fill_random(o.nonce_seed ^ 0x5A175A175A175A17ull ^ (97ull * c0 + d), k->worker.salts.get(), slots,
                                             k->stream),
@@ -213,6 +218,8 @@ void chain_work(pvac_hip_ctx* k, chain_shared* sh, chain_range* rg, bool stage, 
                     sh->failed(PVAC_EINVAL, "ct_mul_chain: fill_nonces callback failed");
                     return;
                 }
+            } else if (o.flags & PVAC_CHAIN_DRBG) {
+                if (!rcchk(drbg_fill(k, k->worker.nonces.get(), nw, "fill nonces"), "generator")) return;
             } else if (!chain_ok(sh, launch_fill_random(o.nonce_seed + 97ull * c0 + d, k->worker.nonces.get(), nw, k->stream),
                                "fill nonces")) {
                 return;
@@ -307,7 +314,7 @@ int pvac_hip_ct_mul_chain(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac_ch
     if (!c || !o || !st || !batch_ok(X)) return fail(c, PVAC_EINVAL, "ct_mul_chain: bad arguments");
     if (o->depth < 1 || o->depth > PVAC_CHAIN_MAX_DEPTH) return fail(c, PVAC_EINVAL, "ct_mul_chain: depth");
     if (o->flags & ~(PVAC_MUL_ORDER_CANONICAL | PVAC_CHAIN_CHECK_GSUM | PVAC_MUL_WITH_SIGMA | PVAC_CHAIN_STAGE_INPUTS |
-                     PVAC_CHAIN_IMG_BATCH2))
+                     PVAC_CHAIN_IMG_BATCH2 | PVAC_CHAIN_DRBG))
         return fail(c, PVAC_EINVAL, "ct_mul_chain: flags");
     if (o->n_operands > o->depth || (o->n_operands && !o->operands))
         return fail(c, PVAC_EINVAL, "ct_mul_chain: operands");
@@ -392,6 +399,18 @@ int pvac_hip_ct_mul_chain(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac_ch
                 e = k->powg.grow(2 * (size_t)c->powg_n, 2 * (size_t)c->powg_n);
                 if (e != hipSuccess) return hip_fail(c, e, "ct_mul_chain: worker powg");
                 k->powg_n = c->powg_n;
+            }
+            // the worker's generator: 48 bytes of the caller's, drawn when the worker is created (and
+            // again after the caller's generator was seeded anew, so an explicit seed reaches it)
+            if ((o->flags & PVAC_CHAIN_DRBG) && k->drbg.worker_from != c->drbg.epoch) {
+                uint8_t seed[kDrbgSeedLen];
+                int rc = c->drbg.gen.generate_host(seed, sizeof seed);
+                uint64_t cnt[4];
+                c->drbg.gen.counts(cnt);
+                if (!rc) rc = k->drbg.gen.seed(seed, cnt[3] != 0);
+                wipe(seed, sizeof seed);
+                if (rc) return fail(c, rc, "ct_mul_chain: worker generator: no entropy (getrandom failed)");
+                k->drbg.worker_from = c->drbg.epoch;
             }
             e = hipSuccess;
             if (c->powg.get()) e = hipMemcpyPeer(k->powg.get(), k->device, c->powg.get(), c->device, (size_t)c->powg_n * 16);
