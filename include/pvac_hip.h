@@ -213,9 +213,15 @@ int pvac_hip_ct_mul_path_count(pvac_hip_ctx* ctx, uint64_t* out);
  * scratch is about 16 words per key slot (|A.L||B.L|B slots), at most ~350 MB at the default limit and
  * over 100 GB near 2^31 slots, so a caller raises the limit knowing what its ciphers cost.
  * set: PVAC_EINVAL outside [PVAC_LAYER_LIMIT_DEFAULT, PVAC_LAYER_LIMIT_MAX]. The workers of
- * pvac_hip_ct_mul_chain take the calling context's limit at each call. ct_lincomb, compact and ct_recrypt
- * keep their 30000-layer refusals at any limit; an over-budget ct_add pair (guard_budget) of any depth
- * takes the merge kernel, whose layer table is in global scratch already. */
+ * pvac_hip_ct_mul_chain take the calling context's limit at each call. The 30000-layer refusals of
+ * ct_lincomb, compact and ct_recrypt move with the limit as ct_add's does: a lincomb term (and a fold-route
+ * segment in all), a cipher compact hands to its merge path and a ct_recrypt sum (a cipher plus a pool
+ * member) may have max(30000, limit) layers. Above 30000 a lincomb term is closed by the deep-term
+ * route, whose keep and remap words are in global scratch (4 bytes per input layer of the call), and the
+ * sums of the fold route and of ct_recrypt run k_ct_add_deep. An over-budget ct_add pair (guard_budget) and a cipher of
+ * compact beyond its batched kernel take the merge kernel at any depth: it never builds the 2|L|B key
+ * space, its scratch is 56 bytes per input edge (the 32-bit sort keys and values, in and out, and
+ * five 8-byte columns) plus 4 bytes per layer and the radix sort's own temporary storage. */
 #define PVAC_LAYER_LIMIT_DEFAULT 16384u
 #define PVAC_LAYER_LIMIT_MAX (1u << 24)
 int pvac_hip_ctx_set_layer_limit(pvac_hip_ctx* ctx, uint32_t max_layers); /* DEFAULT..MAX, else PVAC_EINVAL */
@@ -223,6 +229,12 @@ int pvac_hip_ctx_layer_limit(pvac_hip_ctx* ctx, uint32_t* out);
 /* Since the context was created: out[0] = ct_mul pairs run by the deep kernels (a chain's workers
  * included), out[1] = ct_add / ct_sub calls run by the deep kernel. */
 int pvac_hip_deep_path_count(pvac_hip_ctx* ctx, uint64_t out[2]);
+/* Since the context was created: out[0] = ct_lincomb terms planned on the deep-term route (counted by
+ * exec, like pvac_hip_ct_lincomb_path_count), out[1] = sums of ct_lincomb's fold route handed to
+ * k_ct_add_deep (they are counted in pvac_hip_deep_path_count's out[1] as well), out[2] = ciphers of more
+ * than 30000 layers compacted (compact_exec and ct_recrypt_exec), out[3] = ct_recrypt's sums of more than
+ * 30000 layers (|cipher.L| + |pool member.L|, per cipher and iteration). All zero at the default limit. */
+int pvac_hip_deep_route_count(pvac_hip_ctx* ctx, uint64_t out[4]);
 /* Per-pair outcome of the last ct_mul_exec, copied (stream-ordered) to the DEVICE array out[n]:
  * 0 = reference hash order, 1 = canonical (layer, idx, P<M) order (guard_budget or
  * PVAC_MUL_ORDER_CANONICAL), 2 = rejected. Rejection is stricter than the reference: an edge with
@@ -417,16 +429,19 @@ int pvac_hip_ct_scale(pvac_hip_ctx* ctx, pvac_ct_batch* X, uint64_t s_lo, uint64
  * and C both have sigma, with equal sigma_words (PVAC_EINVAL when they differ). C's arrays are not X's.
  * plan: writes C->l_off / C->e_off as exclusive scans of the segments' sums of |X[term].L| and
  * |X[term].E| (dense CSR capacities; a result is never larger), fills *plan (kind 6, n_small / n_large
- * = segments on the one-pass / fold route) and synchronises once, or twice when a term takes the
- * workgroup route (below). Before anything is written to C: PVAC_EINVAL for seg_off[0] != 0, a
- * decreasing seg_off, seg_off[n] != n_terms or a term index >= X->n (checked on the device, reported
- * with the plan's statistics); PVAC_ENOSYS for a term above 30000 layers (pvac_hip_ct_add_exec's limit),
- * a fold-route segment above 30000 layers in all, or a term's or segment's layer or edge count >= 2^31.
+ * = segments on the one-pass / fold route) and synchronises once, twice when a term takes the
+ * workgroup route, three times when one takes the deep-term route (below). Before anything is written
+ * to C: PVAC_EINVAL for seg_off[0] != 0, a decreasing seg_off, seg_off[n] != n_terms or a term index
+ * >= X->n (checked on the device, reported with the plan's statistics); PVAC_ENOSYS for a term above
+ * max(30000, the context's layer limit) layers (pvac_hip_ct_add_exec's limit), a fold-route segment
+ * above as many layers in all, or a term's or segment's layer or edge count >= 2^31.
  * exec: writes the rows and exact C->l_cnt / C->e_cnt. It takes this context's latest plan only, with
  * the X and S it was planned for.
  * Routes: per term, one pass over its layers and edge headers finds the layers compact_layers keeps
  * (a lane group and a 64-bit mask for terms of at most 64 layers and 8192 edges: the wave route; one
- * workgroup with its table in LDS above: the workgroup route). A segment within edge_budget whose terms
+ * workgroup with its table in LDS above: the workgroup route; above 30000 layers, on a context whose
+ * layer limit admits the term, one workgroup with its table in global scratch: the deep-term route,
+ * counted by pvac_hip_deep_route_count). A segment within edge_budget whose terms
  * are all inside the Cipher contract (every edge's layer_id and every kept PROD parent below its own
  * |L|) is gathered in one pass: each term compacted on its own lands at its offset, which is what the
  * fold computes. Any other segment is computed by the literal loop above on pvac_hip_ct_add_plan /
@@ -478,7 +493,9 @@ int pvac_hip_ubk_apply(pvac_hip_ctx* ctx, pvac_ct_batch* X, const uint32_t* acti
  * out of range (undefined in the reference) is dropped. X and C must carry sigma (PVAC_EINVAL).
  * A cipher whose key space |L| * 2B is at most 14336 cells (21 layers at B = 337), with at most
  * 1024 layers and 65536 edges, is served by one workgroup of a batched kernel; any other by the
- * per-cipher merge path of ct_add's guard_budget. exec takes this context's latest plan only. */
+ * per-cipher merge path of ct_add's guard_budget. plan: PVAC_ENOSYS for a cipher of the merge path
+ * with more than max(30000, the context's layer limit) layers, 2^31 edges or more, or |L| * 2B >= 2^32
+ * - 1 keys. exec takes this context's latest plan only. */
 int pvac_hip_compact_plan(pvac_hip_ctx* ctx, const pvac_ct_batch* X, pvac_ct_batch* C, pvac_hip_plan* plan);
 int pvac_hip_compact_exec(pvac_hip_ctx* ctx, const pvac_hip_plan* plan, const pvac_ct_batch* X, pvac_ct_batch* C);
 /* Ciphers compacted since the context was created (compact_exec and ct_recrypt_exec): out[0] by the
@@ -491,7 +508,8 @@ int pvac_hip_compact_path_count(pvac_hip_ctx* ctx, uint64_t out[2]);
  * counts, and exec rejects a larger pool; synchronises once). exec, per cipher: up to 8 times, while
  * its sigma density lies outside [0.495, 0.505] (decided on the host from the exact popcounts with
  * the reference's long double expression), ct_add the pool member picks[8 i + it] % pool->n
- * (pvac_hip_ct_add_plan / _exec, guard_budget included), then ubk_apply; at the end compact_edges
+ * (pvac_hip_ct_add_plan / _exec, guard_budget and the max(30000, layer limit) bound of a sum
+ * included), then ubk_apply; at the end compact_edges
  * and compact_layers, always. picks (HOST, 8 n words) replace the loop's csprng_u64 draws
  * (recrypt.hpp:32): only the iterations that run consume theirs, in order. iters (HOST, n u32,
  * nullable) receives the iteration counts. An empty pool or e_cnt[i] == 0 copies cipher i verbatim,

@@ -494,14 +494,22 @@ public:
     pvac_hip_ctx* ctx() const { return ctx_; }
     uint32_t sigma_words() const { return (prm_.m_bits + 63) / 64; }
 
-    // The layers a ct_mul pair may have before compaction, and (with 30000) a ct_add pair in all
+    // The layers a ct_mul pair may have before compaction, and (with 30000) a ct_add pair in all; ct_lincomb,
+    // compact and ct_recrypt below take a term, cipher or sum of max(30000, limit) layers as well
     // (pvac_hip_ctx_set_layer_limit: PVAC_LAYER_LIMIT_DEFAULT .. PVAC_LAYER_LIMIT_MAX; a deep pair's
     // scratch is about 16 words per key slot). The thread-local engines of the free functions keep
-    // the default.
+    // the default: engine_for(pk).set_layer_limit(n) raises it for the calling thread.
     void set_layer_limit(uint32_t max_layers) { check(pvac_hip_ctx_set_layer_limit(ctx_, max_layers)); }
     uint32_t layer_limit() const {
         uint32_t v = 0;
         if (const int rc = pvac_hip_ctx_layer_limit(ctx_, &v)) throw Error(rc, "pvac_hip_ctx_layer_limit");
+        return v;
+    }
+    // pvac_hip_deep_route_count: ct_lincomb terms on the deep-term route, its fold sums run by the deep add
+    // kernel, ciphers above 30000 layers compacted, ct_recrypt sums above 30000 layers, since the engine was made
+    std::array<uint64_t, 4> deep_route_counts() const {
+        std::array<uint64_t, 4> v{};
+        if (const int rc = pvac_hip_deep_route_count(ctx_, v.data())) throw Error(rc, "pvac_hip_deep_route_count");
         return v;
     }
 

@@ -165,6 +165,7 @@ def load_library(path: str = _LIB_PATH) -> C.CDLL:
         "pvac_hip_ctx_set_layer_limit": ([vp, u32], i32),
         "pvac_hip_ctx_layer_limit": ([vp, C.POINTER(u32)], i32),
         "pvac_hip_deep_path_count": ([vp, C.POINTER(u64)], i32),
+        "pvac_hip_deep_route_count": ([vp, C.POINTER(u64)], i32),
         "pvac_hip_ct_mul_status": ([vp, vp, C.c_size_t], i32),
         "pvac_hip_ct_mul_chain": ([vp, C.POINTER(CtBatch), C.POINTER(ChainOpts), C.POINTER(ChainStats)], i32),
         "pvac_hip_alu_ceiling": ([vp, i32, C.POINTER(C.c_double)], i32),
@@ -781,7 +782,8 @@ class Engine:
 
     def set_layer_limit(self, n):
         """Layers a ct_mul pair may have before compaction (|A.L| + |B.L| + |A.L||B.L|), LAYER_LIMIT_DEFAULT ..
-        LAYER_LIMIT_MAX; ct_add / ct_sub then take max(30000, n) layers a pair. A pair above the default runs
+        LAYER_LIMIT_MAX; ct_add / ct_sub, and with them ct_lincomb, compact and ct_recrypt, then take
+        max(30000, n) layers a pair, term, cipher or sum. A pair above the default runs
         the deep kernels; its scratch is about 16 words per key slot (|A.L||B.L|B slots)."""
         self._check(self.lib.pvac_hip_ctx_set_layer_limit(self.ctx, int(n)))
 
@@ -797,6 +799,14 @@ class Engine:
         v = (C.c_uint64 * 2)()
         self._check(self.lib.pvac_hip_deep_path_count(self.ctx, v))
         return int(v[0]), int(v[1])
+
+    def deep_route_counts(self):
+        """Since the context was created: (ct_lincomb terms on the deep-term route, sums of its fold route run
+        by the deep add kernel, ciphers above 30,000 layers compacted, ct_recrypt sums above 30,000 layers).
+        All zero while the layer limit is at its default."""
+        v = (C.c_uint64 * 4)()
+        self._check(self.lib.pvac_hip_deep_route_count(self.ctx, v))
+        return tuple(int(x) for x in v)
 
     def ct_mul_status(self, n):
         """Per-pair outcome of the last ct_mul (0 hash order, 1 canonical order, 2 rejected)."""

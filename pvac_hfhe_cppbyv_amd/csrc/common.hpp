@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/pvac_hip.h"
+#include "deep_ops.hpp"
 #include "fp127.hpp"
 #include "gather_tiles.hpp"
 
@@ -568,10 +569,8 @@ hipError_t launch_ct_add_deep(const pvac_ct_batch& A, const pvac_ct_batch& B, pv
 
 // ---- ct_lincomb (k_lincomb.hip): segmented sums of optionally scaled ciphers, the work unit the term.
 // Terms of at most kLinWaveLayers layers and kLinWaveEdges edges are closed by a lane group (the
-// wave route: a 64-bit keep mask), the others by one workgroup each (a remap table in scratch).
-constexpr uint32_t kLinWaveLayers = 64;
-constexpr uint32_t kLinWaveEdges = 8192;
-constexpr uint32_t kLinMaxLayers = 30000;          // per term: pvac_hip_ct_add_exec's limit
+// wave route: a 64-bit keep mask), the others by one workgroup each (a remap table in scratch): the
+// workgroup route up to kLinMaxLayers layers, the deep-term route above (deep_ops.hpp has the rule).
 constexpr uint64_t kLinKeptMask = (1ull << 40) - 1;   // kraw / sK: kept layers below bit 40, flagged terms above
 // segment classes (lincomb_args::cls, pvac_hip_ct_lincomb_status)
 enum : uint32_t { LIN_ONE_PASS = 0, LIN_FOLD_BUDGET = 1, LIN_FOLD_CONTRACT = 2 };
@@ -589,9 +588,9 @@ struct lincomb_args {
     uint64_t* sK;              // exclusive scan of kraw
     uint64_t* mask;            // wave route: the keep mask
     uint32_t* tseg;            // [n_terms] the term's segment
-    uint8_t* troute;           // [n_terms] 0 = wave route, 1 = workgroup route
-    uint64_t* wg_ids;          // [n_terms] the workgroup route's terms (plan_stats::n_small of them)
-    uint32_t* remap;           // workgroup route: new layer id (0xFFFFFFFF = dropped) at sL[k] + layer
+    uint8_t* troute;           // [n_terms] 0 = wave route, 1 = its remap is in the slab (workgroup and deep-term routes)
+    uint64_t* wg_ids;          // [n_terms] the terms beyond the wave route (plan_stats::n_small of them)
+    uint32_t* remap;           // the slab: new layer id (0xFFFFFFFF = dropped) at sL[k] + layer
     uint32_t* cls;             // [n] segment class
     uint64_t* fold_ids;        // [n] the fold route's segments (plan_stats::n_large of them)
     // the copy pass's tiles: the term that holds the first layer slot / edge of tile b (kLinLayerTile
@@ -611,6 +610,11 @@ constexpr uint32_t kLinEdgeTile = 1024;
 hipError_t launch_lincomb_plan(const lincomb_args& a, hipStream_t st);
 // 2. (after the scans of sL / sE) the workgroup route's n_wg terms: keep table in LDS -> remap, kraw
 hipError_t launch_lincomb_plan_wg(const lincomb_args& a, uint64_t n_wg, uint32_t max_layers, hipStream_t st);
+// 2a. a call with a term above kLinMaxLayers: a.wg_ids[0, n_wg) split by lincomb_route into out + 2 (the
+//     workgroup route's) and out + 2 + n_terms (the deep-term route's), their counts in out[0] / out[1] (zeroed)
+hipError_t launch_lincomb_split(const lincomb_args& a, uint64_t n_wg, uint64_t* out, hipStream_t st);
+// 2b. the deep-term route's n_deep terms: keep table and remap in the slab (a.remap), any layer count
+hipError_t launch_lincomb_plan_deep(const lincomb_args& a, const uint64_t* deep_ids, uint64_t n_deep, hipStream_t st);
 // 3. (after the scan of kraw into sK) per segment: class, fold list, segment maxima
 hipError_t launch_lincomb_classify(const lincomb_args& a, hipStream_t st);
 // 4. C.l_off / C.e_off and the copy pass's tile tables

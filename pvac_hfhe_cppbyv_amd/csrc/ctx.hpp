@@ -141,8 +141,11 @@ struct pvac_hip_ctx {
     bool own_stream = false;
     pvac_hip_params prm{};
     uint32_t layer_limit = PVAC_LAYER_LIMIT_DEFAULT;   // pvac_hip_ctx_set_layer_limit (a chain worker: its parent's)
+    // pvac_hip_deep_route_count: lincomb terms on the deep-term route, lincomb fold sums run by k_ct_add_deep,
+    // compact ciphers and recrypt sums above kAddLdsLayers layers
+    uint64_t deep_route[4] = {};
     std::string err;
-    pvhip::dev_buf<uint32_t> nb_table;   // libstdc++ bucket counts and their fastmod64 multipliers
+    pvhip::dev_buf<uint32_t> nb_table;  // libstdc++ bucket counts and their fastmod64 multipliers
     pvhip::dev_buf<uint64_t> nb_magic;
     pvhip::plan_scratch ps;
     pvhip::dev_buf<uint64_t> scan_scratch;
@@ -214,7 +217,8 @@ struct pvac_hip_ctx {
         pvhip::dev_buf<uint32_t> tseg, remap, cls, tile_l, tile_e;
         pvhip::dev_buf<uint8_t> troute;
         pvhip::dev_buf<uint64_t> wg_ids, fold_ids;
-        uint64_t n = 0, n_terms = 0, n_wg = 0, n_fold = 0;   // ... and its shape
+        pvhip::dev_buf<uint64_t> route_ids;          // a plan with a deep term: two counts, then wg_ids split by route
+        uint64_t n = 0, n_terms = 0, n_wg = 0, n_deep = 0, n_fold = 0;   // ... and its shape
         uint64_t status_n = 0;                       // segments of the last exec (cls holds their status)
         uint64_t path[4] = {};                       // segments one-pass / fold, terms wave / workgroup route
         struct set {                                 // the fold route's accumulator, ping-pong
@@ -464,10 +468,10 @@ int ct_mul_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_ct_batch*
 // rt_drbg.cpp: n words of the context's generator into out on the context's stream (pvac_hip_drbg_fill)
 int drbg_fill(pvac_hip_ctx* c, uint64_t* out, size_t n_words, const char* where);
 
-// rt_add.cpp: pvac_hip_ct_add_exec with the most layers a pair may have. The ABI entry passes
-// max(kAddLdsLayers, the context's layer limit); ct_recrypt's and ct_lincomb's sums pass kAddLdsLayers,
-// so their refusals do not move with the limit
+// rt_add.cpp: pvac_hip_ct_add_exec with the most layers a pair may have. The ABI entry and the sums of
+// ct_recrypt and ct_lincomb all pass deep_layer_bound(the context's layer limit) (deep_ops.hpp)
 constexpr uint32_t kAddLdsLayers = 30000;   // |A.L| + |B.L| k_ct_add's LDS keep table holds (120 KB)
+static_assert(kAddLdsLayers == kLinMaxLayers, "one bound for every LDS keep table");
 int ct_add_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_ct_batch* A, const pvac_ct_batch* B, int negate_b,
                 pvac_ct_batch* C, uint32_t lmax);
 

@@ -8,6 +8,8 @@
 //                                 mask (terms of at most 64 layers), and the contract flag
 //              k_lincomb_plan_wg  the same for larger terms, one workgroup each, keep table in LDS,
 //                                 the remap left in scratch
+//              k_lincomb_split, k_lincomb_plan_deep  a term above kLinMaxLayers layers (a context with
+//                                 a raised layer limit): the keep table in scratch too, where the remap goes
 //              k_lincomb_index    the segment of every term; seg_off's own checks
 //              (u64 scans over the terms: layer, edge and kept-layer offsets)
 //              k_lincomb_classify per segment: one pass, or the host's fold (over budget, contract)
@@ -199,6 +201,53 @@ __global__ __launch_bounds__(kLinBlock) void k_lincomb_plan_wg(lincomb_args a, u
         });
         // the remap to scratch; its closing barrier also frees keep[] and bad for the next term
         const uint32_t kept = block_remap<kLinBlock>(keep, a.remap + a.sL[k], L, part);
+        if (tid == 0) a.kraw[k] = (uint64_t)kept | ((uint64_t)bad << 40);
+    }
+}
+
+// A call with a term above kLinMaxLayers: the terms beyond the wave route, split by route. out[0] / out[1]
+// count the workgroup / deep-term route's terms, listed (in any order) from out + 2 / out + 2 + n_terms.
+__global__ __launch_bounds__(kLinBlock) void k_lincomb_split(lincomb_args a, uint64_t n_wg, uint64_t* out) {
+    const uint64_t w = (uint64_t)blockIdx.x * kLinBlock + threadIdx.x;
+    if (w >= n_wg) return;
+    const uint64_t k = a.wg_ids[w];
+    const uint64_t t = a.term[k];
+    const bool deep = lincomb_route(a.X.l_cnt[t], a.X.e_cnt[t]) == LIN_ROUTE_DEEP;
+    const uint64_t at = atomicAdd((unsigned long long*)out + (deep ? 1 : 0), 1ull);
+    out[2 + (deep ? a.n_terms : 0ull) + at] = k;
+}
+
+// The deep-term route: k_lincomb_plan_wg with the keep table where the remap goes, in the slab at
+// sL[k] (global memory: compact_layers.hpp's contract covers a table there), so nothing is sized by
+// the layer count. One workgroup per term, grid-stride over its layers and edge headers; the closure
+// is block_close's, monotone, and ends when a sweep of this workgroup marks nothing.
+constexpr int kLinDeepBlock = 1024;
+__global__ __launch_bounds__(kLinDeepBlock) void k_lincomb_plan_deep(lincomb_args a, const uint64_t* deep_ids,
+                                                                      uint64_t n_deep) {
+    __shared__ uint32_t changed, bad;
+    __shared__ uint32_t part[kLinDeepBlock / 64];
+    const pvac_ct_batch& X = a.X;
+    const uint32_t tid = threadIdx.x;
+    for (uint64_t w = blockIdx.x; w < n_deep; w += gridDim.x) {
+        const uint64_t k = deep_ids[w];
+        const uint64_t t = a.term[k];
+        const uint32_t L = (uint32_t)X.l_cnt[t];   // at most the context's layer limit (host-checked)
+        const uint64_t E = X.e_cnt[t], xeo = X.e_off[t];
+        const pvac_layer* lay = X.layers + X.l_off[t];
+        uint32_t* keep = a.remap + a.sL[k];        // L words of the slab: sL is the scan of the terms' layer counts
+        for (uint32_t l = tid; l < L; l += kLinDeepBlock) keep[l] = 0;
+        if (tid == 0) bad = 0;
+        __syncthreads();
+        for (uint64_t e = tid; e < E; e += kLinDeepBlock) {
+            const uint32_t lid = meta_layer(X.meta[xeo + e]);
+            if (lid < L) keep[lid] = 1;
+            else bad = 1;
+        }
+        block_close<kLinDeepBlock>(keep, L, &changed, [&](uint32_t l, uint32_t& rule, uint32_t& pa, uint32_t& pb) {
+            rule = lay[l].rule; pa = lay[l].pa; pb = lay[l].pb;
+            if (rule == 1 && (pa >= L || pb >= L)) bad = 1;   // a kept PROD layer with a parent beyond the term
+        });
+        const uint32_t kept = block_remap<kLinDeepBlock>(keep, keep, L, part);   // its closing barrier frees `bad`
         if (tid == 0) a.kraw[k] = (uint64_t)kept | ((uint64_t)bad << 40);
     }
 }
@@ -424,6 +473,19 @@ hipError_t launch_lincomb_plan_wg(const lincomb_args& a, uint64_t n_wg, uint32_t
     if (max_layers > kLinMaxLayers) return hipErrorInvalidValue;
     const size_t lds = ((size_t)max_layers * 4 + 15) & ~(size_t)15;
     hipLaunchKernelGGL(k_lincomb_plan_wg, dim3((unsigned)(n_wg < 2048 ? n_wg : 2048)), dim3(kLinBlock), lds, st, a, n_wg);
+    return hipGetLastError();
+}
+
+hipError_t launch_lincomb_split(const lincomb_args& a, uint64_t n_wg, uint64_t* out, hipStream_t st) {
+    if (!n_wg) return hipSuccess;
+    hipLaunchKernelGGL(k_lincomb_split, dim3(blocks_for(n_wg)), dim3(kLinBlock), 0, st, a, n_wg, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_lincomb_plan_deep(const lincomb_args& a, const uint64_t* deep_ids, uint64_t n_deep, hipStream_t st) {
+    if (!n_deep) return hipSuccess;
+    hipLaunchKernelGGL(k_lincomb_plan_deep, dim3((unsigned)(n_deep < 2048 ? n_deep : 2048)), dim3(kLinDeepBlock), 0, st, a,
+                       deep_ids, n_deep);
     return hipGetLastError();
 }
 

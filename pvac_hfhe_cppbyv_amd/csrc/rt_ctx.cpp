@@ -159,6 +159,12 @@ int pvac_hip_deep_path_count(pvac_hip_ctx* c, uint64_t out[2]) {
     return PVAC_OK;
 }
 
+int pvac_hip_deep_route_count(pvac_hip_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return PVAC_EINVAL;
+    for (int k = 0; k < 4; ++k) out[k] = c->deep_route[k];
+    return PVAC_OK;
+}
+
 int pvac_hip_ctx_set_enc_plan_limit(pvac_hip_ctx* c, uint32_t max_pre_edges) try {
     if (!c) return PVAC_EINVAL;
     if (max_pre_edges < PVAC_ENC_PLAN_LIMIT_DEFAULT || max_pre_edges > PVAC_ENC_PLAN_LIMIT_MAX)

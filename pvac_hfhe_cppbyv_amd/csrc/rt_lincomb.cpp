@@ -171,8 +171,10 @@ int fold_segments(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac_lincomb* S
             grow_set(1 - cur, ap.total_layer_slots, ap.total_edge_slots);
             if (e != hipSuccess) break;
             rows_of(Cv, 1 - cur);
-            rc = ct_add_exec(c, &ap, &Av, &Tv, 0, &Cv, kAddLdsLayers);   // (its 30000-layer refusal stays)
+            const uint64_t deep0 = c->merge.deep_calls;
+            rc = ct_add_exec(c, &ap, &Av, &Tv, 0, &Cv, deep_layer_bound(c->layer_limit));
             if (rc) return rc;
+            c->deep_route[1] += c->merge.deep_calls - deep0;   // a running sum above kAddLdsLayers: k_ct_add_deep
             cur ^= 1;
         }
         if (e != hipSuccess) break;
@@ -209,7 +211,7 @@ int pvac_hip_ct_lincomb_plan(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac
     const uint64_t n = S->n, nt = S->n_terms;
     if (!n) {
         c->ps.invalidate();
-        lc.n = lc.n_terms = lc.n_wg = lc.n_fold = 0;
+        lc.n = lc.n_terms = lc.n_wg = lc.n_deep = lc.n_fold = 0;
         C->n = 0;
         c->ps.commit(plan);
         return PVAC_OK;
@@ -241,16 +243,38 @@ int pvac_hip_ct_lincomb_plan(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac
     if (rc) return rc;
     // nothing has been written to C yet
     if (st.n_invalid) return fail(c, PVAC_EINVAL, "ct_lincomb_plan: bad seg_off or term index");
-    if (st.max_layers > kLinMaxLayers) return fail(c, PVAC_ENOSYS, "ct_lincomb_plan: a term above 30000 layers");
+    // the most layers of a term and of a fold-route segment: 30000 unless the context's limit was raised
+    const uint32_t bound = deep_layer_bound(c->layer_limit);
+    if (st.max_layers > bound)
+        return fail(c, PVAC_ENOSYS, "ct_lincomb_plan: a term above " + std::to_string(bound) + " layers");
     if (st.max_na >= (1u << 31) || st.max_prod >= (1u << 31) || st.max_nb >= (1u << 31))
         return fail(c, PVAC_ENOSYS, "ct_lincomb_plan: a layer or edge count of 2^31 or more");
+    uint64_t n_wg = st.n_small, n_deep = 0;
     if (st.n_small) {
         // the workgroup route: its remap tables are sized from the first read-back, and its contract
         // flags can move segments to the fold route, so the classes are taken again
         e = lc.remap.grow_floor(st.total_layers);
         a = make_args(c, *X, *S, *C);
+        lincomb_args wg = a;
+        const uint64_t* deep_ids = nullptr;
+        if (e == hipSuccess && st.max_layers > kLinMaxLayers) {
+            // a term beyond the LDS keep table: the listed terms split by route (one more read-back),
+            // the deep ones closed in the slab, at the offsets the workgroup route's remaps have
+            uint64_t cnt[2] = {0, 0};
+            e = lc.route_ids.grow_floor(2 + 2 * nt);
+            uint64_t* const R = lc.route_ids.get();
+            if (e == hipSuccess) e = hipMemsetAsync(R, 0, 16, c->stream);
+            if (e == hipSuccess) e = launch_lincomb_split(a, st.n_small, R, c->stream);
+            if (e == hipSuccess) e = read_back(c, cnt, R, sizeof cnt);
+            if (e == hipSuccess && cnt[0] + cnt[1] != st.n_small) e = hipErrorUnknown;
+            n_wg = cnt[0];
+            n_deep = cnt[1];
+            wg.wg_ids = R + 2;
+            deep_ids = R + 2 + nt;
+        }
         if (e == hipSuccess) e = hipMemsetAsync(&c->ps.stats.get()->n_large, 0, 8, c->stream);
-        if (e == hipSuccess) e = launch_lincomb_plan_wg(a, st.n_small, st.max_layers, c->stream);
+        if (e == hipSuccess) e = launch_lincomb_plan_wg(wg, n_wg, std::min(st.max_layers, kLinMaxLayers), c->stream);
+        if (e == hipSuccess) e = launch_lincomb_plan_deep(a, deep_ids, n_deep, c->stream);
         if (e == hipSuccess) e = scan_and_classify(c, a);
         plan_stats st2{};
         if (e == hipSuccess) e = read_back(c, &st2, c->ps.stats.get(), sizeof st2);
@@ -258,8 +282,8 @@ int pvac_hip_ct_lincomb_plan(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac
         st.n_large = st2.n_large;
         st.max_buckets = st2.max_buckets;
     }
-    if (st.n_large && st.max_buckets > kLinMaxLayers)
-        return fail(c, PVAC_ENOSYS, "ct_lincomb_plan: a fold-route segment above 30000 layers");
+    if (st.n_large && st.max_buckets > bound)
+        return fail(c, PVAC_ENOSYS, "ct_lincomb_plan: a fold-route segment above " + std::to_string(bound) + " layers");
     const uint64_t tl = (st.total_layers + kLinLayerTile - 1) / kLinLayerTile + 1;
     const uint64_t te = (st.total_edges + kLinEdgeTile - 1) / kLinEdgeTile + 1;
     e = lc.tile_l.grow_floor(tl);
@@ -274,7 +298,8 @@ int pvac_hip_ct_lincomb_plan(pvac_hip_ctx* c, const pvac_ct_batch* X, const pvac
     plan->max_layers = st.max_layers;
     lc.n = n;
     lc.n_terms = nt;
-    lc.n_wg = st.n_small;
+    lc.n_wg = n_wg;
+    lc.n_deep = n_deep;
     lc.n_fold = st.n_large;
     C->n = n;
     c->ps.commit(plan);
@@ -304,8 +329,9 @@ int pvac_hip_ct_lincomb_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const p
     lc.status_n = S->n;
     lc.path[0] += plan->n_small;
     lc.path[1] += plan->n_large;
-    lc.path[2] += lc.n_terms - lc.n_wg;
+    lc.path[2] += lc.n_terms - lc.n_wg - lc.n_deep;
     lc.path[3] += lc.n_wg;
+    c->deep_route[0] += lc.n_deep;
     if (!plan->n_large) return PVAC_OK;
     return fold_segments(c, X, S, C, plan->n_large);
 } catch (...) { return caught(c, "ct_lincomb_exec"); }

@@ -45,6 +45,10 @@ int compact_classify(pvac_hip_ctx* c, const pvac_ct_batch* X, pvac_ct_batch* C, 
     if (rc) return rc;
     plan_fill(plan, X->n, st);
     if (st.n_large) {
+        // the merge kernel keeps its layer table in global scratch, so the layer bound is ct_add's
+        const uint32_t bound = deep_layer_bound(c->layer_limit);
+        const std::string limit_msg =
+            "compact_plan: a cipher beyond " + std::to_string(bound) + " layers, 2^31 edges or 2^32 keys";
         rc = merge_gather(
             c, st.n_large,
             [&](uint64_t* out) { return launch_compact_gather(*X, *C, c->ps.large_ids.get(), st.n_large, out, c->stream); },
@@ -56,9 +60,9 @@ int compact_classify(pvac_hip_ctx* c, const pvac_ct_batch* X, pvac_ct_batch* C, 
                 m.aeo = o[3];
                 m.beo = 0;
                 m.ceo = o[4];
-                return !(o[1] > 30000 || m.nA >= (1ull << 31) || o[1] * c->prm.B * 2 >= 0xFFFFFFFFull);
+                return !(o[1] > bound || m.nA >= (1ull << 31) || o[1] * c->prm.B * 2 >= 0xFFFFFFFFull);
             },
-            "compact_plan (merge)", "compact_plan: a cipher beyond 30000 layers, 2^31 edges or 2^32 keys");
+            "compact_plan (merge)", limit_msg.c_str());
         if (rc) return rc;
     }
     c->ps.commit(plan);
@@ -89,6 +93,7 @@ int compact_execute(pvac_hip_ctx* c, const pvac_hip_plan* plan, const pvac_ct_ba
     const int rc = merge_execute(c, *X, Bz, *C, 0, "compact merge");
     if (rc) return rc;
     c->recrypt.compact_path[1] += plan->n_large;
+    for (const merge_pair_info& m : c->merge.set) c->deep_route[2] += m.L > kAddLdsLayers;
     return PVAC_OK;
 }
 
@@ -337,8 +342,10 @@ int pvac_hip_ct_recrypt_exec(pvac_hip_ctx* c, const pvac_hip_plan* plan, const p
         Cv.w_lo = buf.w_lo.get();
         Cv.w_hi = buf.w_hi.get();
         Cv.sigma = buf.sigma.get();
-        rc = ct_add_exec(c, &ap, &Av, &Bv, 0, &Cv, kAddLdsLayers);   // (its 30000-layer refusal stays)
+        rc = ct_add_exec(c, &ap, &Av, &Bv, 0, &Cv, deep_layer_bound(c->layer_limit));
         if (rc) return rc;
+        for (uint64_t k = 0; k < m2; ++k)   // the sums above k_ct_add's table (the call then ran k_ct_add_deep)
+            c->deep_route[3] += cur[1][cont[k]] + hp[pn + picks[8ull * cur_id[cont[k]] + it] % pn] > kAddLdsLayers;
         e = launch_ubk_apply(Cv, c->recrypt.ubk_perm.get(), m_bits, nullptr, c->num_cus, c->stream);
         // the next view: the sums, where ct_add put them
         std::vector<uint32_t> next_id(m2);
