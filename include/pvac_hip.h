@@ -240,7 +240,10 @@ int pvac_hip_deep_route_count(pvac_hip_ctx* ctx, uint64_t out[4]);
  * PVAC_MUL_ORDER_CANONICAL), 2 = rejected. Rejection is stricter than the reference: an edge with
  * layer_id >= |X.L| (undefined behaviour there: C.L[lid] out of range), idx >= B or ch > 1
  * (defined there, out of the Cipher contract: dec_value indexes powg_B[idx]) makes the pair's
- * output empty (l_cnt = e_cnt = 0) instead. */
+ * output empty (l_cnt = e_cnt = 0) instead. The statuses live in the per-pair plan scratch: a later plan
+ * (ct_mul, ct_add, compact, ct_lincomb, ct_recrypt) of more pairs than the scratch held regrows it and
+ * discards them, and the call then fails with PVAC_EINVAL, as it does for n above the last exec's
+ * pairs, until the next ct_mul_exec. */
 int pvac_hip_ct_mul_status(pvac_hip_ctx* ctx, uint32_t* out, size_t n);
 /* The reference's ct_mul invariant check_mul_gsum_all (utils/metrics.hpp:88-113) on every pair of
  * a batch: gsum(C, product layer of (la, lb)) == gsum(A, la) * gsum(B, lb) with

@@ -809,7 +809,8 @@ class Engine:
         return tuple(int(x) for x in v)
 
     def ct_mul_status(self, n):
-        """Per-pair outcome of the last ct_mul (0 hash order, 1 canonical order, 2 rejected)."""
+        """Per-pair outcome of the last ct_mul (0 hash order, 1 canonical order, 2 rejected). A later plan of
+        more pairs than any before regrows the scratch that holds them: PvacError until the next ct_mul."""
         out = self.torch.zeros(max(n, 1), dtype=self.torch.int32, device=self.device)
         self._check(self.lib.pvac_hip_ct_mul_status(self.ctx, C.c_void_p(out.data_ptr()), n))
         return out.cpu().numpy().view(np.uint32)[:n]

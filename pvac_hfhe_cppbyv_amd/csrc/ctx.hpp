@@ -424,7 +424,11 @@ inline bool sigma_ok(const pvac_hip_ctx* c, const pvac_ct_batch* X) {
 template <class Launch>
 int plan_pass(pvac_hip_ctx* c, uint64_t n, pvac_ct_batch* C, bool scan, const char* where, Launch&& launch, plan_stats& st) {
     plan_scratch& ps = c->ps;
+    const size_t cap0 = ps.capacity();
     int rc = hip_fail(c, ps.begin(n), "alloc pair scratch");
+    // regrown (or given back) arrays no longer hold the last ct_mul_exec's pair_status: ct_mul_status
+    // refuses until the next exec instead of copying out words no kernel wrote
+    if (ps.capacity() != cap0) c->mul.last_pairs = 0;
     if (!rc) rc = ensure_scan(c, n);
     if (rc) return rc;
     hipError_t e = hipMemsetAsync(ps.stats.get(), 0, sizeof(plan_stats), c->stream);
